@@ -4,14 +4,17 @@ A "step" is one pass of the E4S-core hot path (scripts/face_swap
 batch of synthetic swaps resident in HBM: 2 encoder passes, regional style swap, 12 LocalMLPs and the
 mask-guided 1024^2 generator, per swap.  Workload = BASELINE.json configs[3] sharded the way it
 names it (batch 64 over 8 GPUs = 8 swaps per GPU; weak scaling: per-GPU batch fixed) -- at N=1 that
-is 8 swaps on one GPU; the single-swap latency of configs[1] is reported alongside (`latency_b1_ms`).
+is 8 swaps on one GPU; the single-swap latency of configs[1] is reported alongside with --full (`latency_b1_ms`).
 For N>1 each rank runs its shard and the ranks all-gather the [B/N,3,1024,1024] outputs over RCCL
 (the only collective on the path; asynchronous and double-buffered, so step i's gather overlaps step i+1, and every
 gather is drained inside the timed region); timing is barrier+sync bracketed, max over ranks.
 
     python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full                  # + every extra leg below
+    python bench.py --gpus 1 --steps 10 --warmup 2 --dump-outputs DIR      # + the last timed step's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 ... bench.py --gpus 8
 
+A plain run sets up, warms up, times the steps and prints the result line; the legs below take --full.
 Extra legs (rank 0, N=1): `roofline` = the headline kernel ModulatedConv2d(512,512,3)@64x64 (masked,
 region-select) timed with HIP events on its launch stream: the kernel the timed step really runs for that
 layer -- the split-bf16 kernel against the dense bf16 MFMA peak (2500 TF; algorithmic FLOPs, so <= 1/3 by
@@ -556,6 +559,26 @@ def cpu_baseline(sd, lat, inputs, hip_img0, hip_img0_b1):
             "seconds": round(dt * reps, 2)}, err
 
 
+DUMP_BUDGET = 48 << 20            # bytes of --dump-outputs in all
+
+
+def dump_outputs(d, arrays):
+    """Write {name: tensor} as d/<name>.npy in float32.  An array larger than its share of DUMP_BUDGET is written as a 1-D sample:
+    the elements at a seeded set of flat indices (sorted), the same set in every run with the same shapes."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BUDGET // max(1, len(arrays)) // 4
+    for i, (name, t) in enumerate(arrays.items()):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > share:
+            idx = torch.randint(0, flat.numel(), (share,), generator=torch.Generator().manual_seed(1234 + i)).sort().values
+            flat = flat[idx.to(flat.device)]
+            out = flat.float().cpu().numpy()
+        else:
+            out = t.detach().float().cpu().numpy()
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(out, dtype=np.float32))
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -592,6 +615,12 @@ def build_parser():
                     help="N>1: one blocking all-gather per step instead of the default double-buffered asynchronous "
                          "all-gather (e4s_amd.shard.OverlappedGather: step i's gather runs under step i+1's compute; "
                          "every gather completes inside the timed region)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every extra leg (N = 1: single-swap latency, "
+                                                        "fed step, rooflines, exact-fp32 step, gather contention, GPEN, stitch, "
+                                                        "config-5 train and config-3 optimisation legs, CPU baseline + parity)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; a fixed, seeded sample of an "
+                         "output larger than its share of %d MiB)" % (DUMP_BUDGET >> 20))
     ap.add_argument("--steps-only", action="store_true", help="only the timed steps (clean rocprofv3 kernel traces)")
     ap.add_argument("--probe-only", action="store_true", help="run only the headline-kernel probe (for rocprofv3)")
     ap.add_argument("--probe-reps", type=int, default=20)
@@ -766,7 +795,13 @@ def main():
             want.append(pack(o) if pack is not None else o)
         out["stub_gather_ok"] = bool(torch.equal(gathered, torch.cat(want, 0)))
         out["stub_gather_shape"] = list(gathered.shape)
-    if rank == 0 and world == 1 and not args.steps_only and not stub:
+    if rank == 0 and args.dump_outputs:
+        # rank 0's images of the last timed step as the caller receives them: fp32 [B,3,H,W] and the uint8 [B,H,W,3] pack
+        arrays = {"images": img}
+        if pack is not None:
+            arrays["images_uint8"] = packed[0] if packed[0] is not None else pack(img)
+        dump_outputs(args.dump_outputs, arrays)
+    if rank == 0 and world == 1 and args.full and not args.steps_only and not stub:
         # configs[1]: single-swap latency
         one = [t[:1].contiguous() if torch.is_tensor(t) else [n[:1].contiguous() for n in t] for t in inputs]
         swap1 = (lambda *a, noise: face_swap_core(net, *a, noise=noise)) if args.no_graph else None

@@ -1,8 +1,8 @@
 """Import the REAL reference modules (read-only, from /root/reference) on CPU.
 
 TEST INFRASTRUCTURE ONLY; works only where /root/reference exists (the build
-container), never on the GPU box.  Used by tests/golden/make_golden.py to
-generate fixtures and by tests/test_oracle_vs_reference.py to validate the
+container), never on the GPU box.  Used by tests/golden/make_golden.py and
+tests/golden/make_reference_checks.py to generate the fixtures that validate the
 restatement in oracle/e4s_oracle.py.  Nothing from the reference is copied:
 the modules are executed where they lie.
 

@@ -46,6 +46,23 @@ def test_bench_main_world2_overlapped_uint8_gather():
     assert "stub" in rec["data"]
 
 
+def test_bench_main_world2_dump_outputs(tmp_path):
+    """--dump-outputs: rank 0 writes the last timed step's images (fp32 [B,3,H,W]) and their uint8 pack as float32 .npy."""
+    import numpy as np
+    import torch
+    rec = _launch(["--dump-outputs", str(tmp_path)])
+    assert rec["stub_gather_ok"] is True
+    g = torch.Generator().manual_seed(100)                  # rank 0's shard, as bench.py's stub draws it
+    ins = [torch.rand(3, 3, 8, 8, generator=g) * 2 - 1 for _ in range(5)]
+    want = 0.5 * ins[0] + 0.25 * ins[2]
+    images = np.load(tmp_path / "images.npy")
+    assert images.dtype == np.float32 and np.array_equal(images, want.numpy())
+    u8 = np.load(tmp_path / "images_uint8.npy")
+    want_u8 = ((want.clamp(-1, 1) + 1) * 127.5).to(torch.uint8).permute(0, 2, 3, 1)
+    assert u8.dtype == np.float32 and np.array_equal(u8, want_u8.float().numpy())
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["images.npy", "images_uint8.npy"]
+
+
 def test_bench_main_world2_sync_fp32_gather():
     rec = _launch(["--sync-gather", "--gather-fp32"])
     assert rec["stub_gather_ok"] is True and rec["stub_gather_shape"] == [6, 3, 8, 8]

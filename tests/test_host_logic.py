@@ -219,9 +219,36 @@ def test_bench_parser_defaults_follow_the_driver_contract():
     assert not a.gather_fp32 and not a.sync_gather and not a.no_graph and a.opt_graph and not a.stub_swap
     assert not bench.build_parser().parse_args(["--opt-eager"]).opt_graph and a.train_steps >= 10
     assert a.opt_steps == 200 and set(a.opt_modes.split(",")) == {"full", "mse"}
+    assert not a.full and a.dump_outputs is None                          # a plain run times the steps only
+    assert bench.build_parser().parse_args(["--full"]).full
     d = bench.build_parser().parse_args(["--gpus", "8", "--steps", "20", "--warmup", "3"])
     assert (d.gpus, d.steps, d.warmup) == (8, 20, 3)
     assert bench.SIZE == 1024 and bench.KREM == 13                      # BASELINE.json's configuration
+
+
+def test_bench_dump_outputs_fixed_sample_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files; an array within its share of the budget is written whole, a larger one as the same
+    seeded sample of its elements in every run."""
+    import numpy as np
+    bench = _load_bench()
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 2 * 4 * 1000)
+    small = torch.arange(600, dtype=torch.float32).reshape(2, 3, 10, 10)
+    big = torch.randn(4, 3, 40, 40, generator=torch.Generator().manual_seed(0))
+    u8 = torch.randint(0, 256, (4, 40, 40, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(1))
+    bench.dump_outputs(str(tmp_path / "a"), {"images": small, "images_uint8": u8})
+    a = np.load(tmp_path / "a" / "images.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 3, 10, 10) and np.array_equal(a, small.numpy())
+    b = np.load(tmp_path / "a" / "images_uint8.npy")
+    assert b.dtype == np.float32 and b.shape == (1000,) and set(np.unique(b)) <= set(range(256))
+    assert np.isin(b, u8.float().numpy().ravel()).all()
+    bench.dump_outputs(str(tmp_path / "b"), {"images": big, "images_uint8": u8})
+    bench.dump_outputs(str(tmp_path / "c"), {"images": big.clone(), "images_uint8": u8.clone()})
+    total = 0
+    for name in ("images", "images_uint8"):
+        x, y = np.load(tmp_path / "b" / (name + ".npy")), np.load(tmp_path / "c" / (name + ".npy"))
+        assert x.shape == (1000,) and np.array_equal(x, y)
+        total += x.nbytes
+    assert total <= bench.DUMP_BUDGET
 
 
 def test_bench_refuses_to_run_without_a_gpu(monkeypatch):
