@@ -253,6 +253,12 @@ class TrainIteration:
             if hasattr(c, "_target"):
                 c._target = None
 
+    def _invalidate_net_packs(self):
+        """Drop the weight packs of every module of the net that owns a trained parameter (frozen modules -- a frozen generator --
+        keep theirs: a captured step must not re-pack them on every replay)."""
+        from . import packs
+        packs.invalidate_module_packs(packs.modules_owning(self.core, self._net_trainable))
+
     def graphed_g_step(self, img, onehot, warmup=2, fork_losses_in_graph=None, **fwd):
         """The G step (forward, every loss term incl. the target features, backward, [bucketed gradient all-reduces,] fused Adam, EMA)
         captured as ONE HIP graph: returns an optim.GraphedStep; `.step()` replays it on whatever `img` / `onehot` hold then (static
@@ -260,12 +266,14 @@ class TrainIteration:
         the rest (coach.py:74-85,340-357: DDP's bucket all-reduces overlapped with the backward): they sit on RCCL's own stream in the
         graph, forked where a bucket fills and joined before the write-back, so a replay overlaps them with the remaining backward
         exactly as the eager step does.  The eager G step is ~2 500 launches, host-bound: 65-97 ms per step depending on the host
-        against ~55 ms of kernel time.  Every weight pack the step reads from a TRAINED network is rebuilt inside the graph (the net's are
-        stale at capture time -- the warm-up steps just updated them --, D's are invalidated here); after a replay the version counters
-        of everything the graph wrote (parameters, EMA copy) are advanced, so eager consumers between replays (D steps, net_ema
-        evaluation) re-pack from the current weights.  A trainable generator (train_G=True, the reference's default:
-        train_options.py:32-33, coach.py:324-331) is captured like the rest: its packs are rebuilt inside the graph, the style
-        prologue's job tables depend on addresses only (Generator._style_plan) and are built by the warm-up steps."""
+        against ~55 ms of kernel time.  Every weight pack the step reads from a TRAINED network is rebuilt inside the graph: the body
+        drops the packs of the net's modules that own a trained parameter and D's packs before anything reads them
+        (packs.invalidate_module_packs), so the capture records the re-pack kernels into the graph's own pool and never bakes in a
+        pack that an eager consumer frees later; after a replay the version counters of everything the graph wrote (parameters, EMA
+        copy) are advanced, so eager consumers between replays (D steps, net_ema evaluation) re-pack from the current weights.  A
+        trainable generator (train_G=True, the reference's default: train_options.py:32-33, coach.py:324-331) is captured like the
+        rest: its packs are re-packed in place inside the graph (ModulatedConv2d's lifetime buffers), the style prologue's job tables
+        depend on addresses only (Generator._style_plan) and are built by the warm-up steps."""
         from .optim import GraphedStep
         from . import disc_autograd
         if self.core is not self.net:
@@ -274,6 +282,7 @@ class TrainIteration:
 
         def body():
             self.forget_targets()
+            self._invalidate_net_packs()
             if self.disc is not None:
                 disc_autograd.invalidate_packs(self.disc)
             # Inside the capture only ONE loss network -- the identity net, the longest chain -- gets a side stream (the eager step forks them all):
@@ -297,12 +306,15 @@ class TrainIteration:
     def graphed_d_step(self, img, onehot, warmup=1, **fwd):
         """The D step (coach.py:290-307: Net3 forward without a graph, D(real), D(fake), AdvDLoss backward through the closed Function
         families of disc_autograd, [bucketed all-reduces,] fused Adam on D) captured as ONE HIP graph -- ~2 000 launches eagerly.  Needs
-        opt_d = FusedAdam(capturable=True).  The net's weight packs are rebuilt inside the graph when the G step trains it between replays
-        (packs are keyed on versions; GraphedStep advances them)."""
+        opt_d = FusedAdam(capturable=True).  The G step trains the net between replays, so the body drops the packs of the net's modules
+        that own a trained parameter (packs.invalidate_module_packs) as well as D's: the capture records the net's re-pack kernels, into
+        the graph's own pool, and every replay re-packs from the weights of the moment.  Without that the capture would hit the cache
+        and bake in the packs of the last eager step -- stale after the next G step, and freed by the next eager consumer of the net."""
         from .optim import GraphedStep
         from . import disc_autograd
 
         def body():
+            self._invalidate_net_packs()
             disc_autograd.invalidate_packs(self.disc)
             return self.d_step(img, onehot, **fwd)
         return GraphedStep(self.opt_d, body, warmup=warmup)

@@ -609,3 +609,128 @@ def test_graphed_g_step_equals_the_eager_loop(train_G):
         ema_fresh = ema_g(img_g, mask_g, randomize_noise=False)[0]
     assert torch.equal(out_g, out_e) and torch.equal(out_g, out_fresh)
     assert torch.equal(ema_out_g, ema_out_e) and torch.equal(ema_out_g, ema_fresh)
+
+
+def _pack_tensors(net, keep=False):
+    """{data_ptr: (shape, dtype)} of every tensor held in a weight-pack cache of `net` (packs.PACK_ATTRS; lifetime buffers excluded):
+    no tensor is returned, so the caller keeps no pack alive.  keep=True: the list of the tensors themselves."""
+    from e4s_amd import packs
+
+    def walk(v):
+        if torch.is_tensor(v):
+            yield v
+        elif isinstance(v, (tuple, list)):
+            for x in v:
+                yield from walk(x)
+        elif isinstance(v, dict):
+            for x in v.values():
+                yield from walk(x)
+        elif hasattr(v, "packs") and hasattr(v, "key"):          # disc_autograd._PackCache
+            yield from walk(v.packs)
+    held = [t for m in net.modules() for name in packs.PACK_ATTRS for t in walk(vars(m).get(name))]
+    return held if keep else {t.data_ptr(): (tuple(t.shape), t.dtype) for t in held}
+
+
+@pytest.mark.parametrize("train_G,order,bf16", [(False, "g_first", False), (True, "g_first", False), (True, "d_first", False),
+                                                (True, "g_first", True)])
+def test_graphed_joint_iteration_equals_the_eager_loop(train_G, order, bf16):
+    """The joint loop as training runs it (TrainIteration.iteration's order: D, R1 when i % d_reg_every == 0, G) with all three steps
+    replayed as HIP graphs on a real Net3 == the eager loop bit for bit.  The G replays train the net between D replays: the D graph
+    must re-pack the net from the weights of the moment, not serve the packs of its warm-up step (stale after one G step).  An eager
+    evaluation pass between two D replays re-packs the net and drops the old packs; NaN-filled tensors of the same sizes then take
+    their memory, so a D graph that still points at them reads NaNs instead of passing by luck.  Capture orders: bench's (G, D, R1)
+    and D, R1 before G (before the fix the latter faulted: the G capture emptied the allocator's cache and unmapped the packs that
+    the D graph had baked in and the G warm-ups had dropped)."""
+    import copy
+    from e4s_amd.optim import FusedAdam
+    from e4s_amd.train import LossOpts, TrainIteration
+    size, b, iters, eval_at = 256, 2, 4, 2
+    imgs = [synth.synth_image(b, size, tag="gj_img%d" % i).to(DEV) for i in range(2)]
+    masks = [synth.onehot(synth.synth_labels_face(b, 512, seed=51 + i)).to(DEV) for i in range(2)]
+
+    def build():
+        net, _, _ = _net(size, train_G=train_G)
+        net.train()
+        crit, disc, _ = _loss_modules(size)
+        disc.train()
+        opt = FusedAdam([p for p in net.parameters() if p.requires_grad], lr=1e-4, capturable=True)
+        opt_d = FusedAdam(disc.parameters(), lr=1e-3, capturable=True)
+        ema = copy.deepcopy(net).eval()
+        lo = LossOpts(lpips_sizes=(256, 128, 64), d_reg_every=2)
+        it = TrainIteration(net, disc, crit, opt, opt_d, lo=lo, net_ema=ema, bf16_storage=bf16)
+        return it, net, disc, ema
+
+    def trainable(net):
+        return [p.detach().clone() for p in net.parameters() if p.requires_grad]
+
+    def eager_g(it, img, mask):
+        it.forget_targets()
+        return it.g_step(img, mask, randomize_noise=False)[0]
+
+    # twins built identically; the eager one runs the warm-up sequence of the captures, in the order they are captured
+    it_e, net_e, disc_e, ema_e = build()
+    img_e, mask_e = imgs[0].clone(), masks[0].clone()
+    it_g, net_g, disc_g, ema_g = build()
+    img_g, mask_g = imgs[0].clone(), masks[0].clone()
+    # Every capture empties the allocator's cache (torch.cuda.graph), which would unmap a pack that an earlier capture baked in and a
+    # later warm-up dropped: a D graph that kept such a pack would then fault instead of failing an assertion.  The packs the net holds
+    # after each capture stay referenced until the last capture is done; after that, freed memory stays mapped.
+    pinned = []
+    for what in (("g", "d") if order == "g_first" else ("d", "g")):
+        if what == "g":
+            for _ in range(2):
+                eager_g(it_e, img_e, mask_e)
+            gs = it_g.graphed_g_step(img_g, mask_g, warmup=2, randomize_noise=False)
+            pinned += _pack_tensors(net_g, keep=True)
+        else:
+            it_e.d_step(img_e, mask_e, randomize_noise=False)
+            it_e.r1_step(img_e)
+            gd = it_g.graphed_d_step(img_g, mask_g, warmup=1, randomize_noise=False)
+            pinned += _pack_tensors(net_g, keep=True)
+            at_d_capture = trainable(net_g)
+            gr = it_g.graphed_r1_step(img_g, warmup=1)
+    del pinned
+    side_streams = [gs._stream, gd._stream, gr._stream]
+
+    held = []
+    for i in range(iters):
+        for img, mask in ((img_e, mask_e), (img_g, mask_g)):
+            img.copy_(imgs[i % 2])
+            mask.copy_(masks[i % 2])
+        if i == eval_at:
+            # an evaluation pass: re-packs the net from the current weights and drops the packs it held before
+            with torch.no_grad():
+                out_e = net_e(img_e, mask_e, randomize_noise=False)[0]
+                before = _pack_tensors(net_g)
+                out_g = net_g(img_g, mask_g, randomize_noise=False)[0]
+                replaced = [v for k, v in before.items() if k not in _pack_tensors(net_g)]
+                del before
+            assert torch.equal(out_e, out_g)
+            assert any(dt.is_floating_point for _, dt in replaced)
+            # the freed packs went back to the pool of the stream they were allocated on: take them back on every stream in play
+            for s in [torch.cuda.current_stream()] + side_streams:
+                with torch.cuda.stream(s):
+                    held += [torch.full(shape, float("nan"), dtype=dt, device=DEV) for shape, dt in replaced if dt.is_floating_point]
+                torch.cuda.current_stream().wait_stream(s)
+        if i == iters - 1:
+            at_last_d = trainable(net_g)
+        d_e = it_e.d_step(img_e, mask_e, randomize_noise=False)
+        d_g = gd.step().clone()
+        assert torch.equal(d_e, d_g), ("D loss", i, float(d_e), float(d_g))
+        if i % it_g.lo.d_reg_every == 0:
+            r_e = it_e.r1_step(img_e)
+            r_g = gr.step().clone()
+            assert torch.equal(r_e, r_g), ("R1 loss", i, float(r_e), float(r_g))
+        g_e = eager_g(it_e, img_e, mask_e)
+        g_g = gs.step().clone()
+        assert torch.equal(g_e, g_g), ("G loss", i, float(g_e), float(g_g))
+    gs.validate()
+    gd.validate()
+    gr.validate()
+    torch.cuda.synchronize()
+    del held
+    for tag, me, mg in (("net", net_e, net_g), ("ema", ema_e, ema_g), ("disc", disc_e, disc_g)):
+        for (n, pe), (_, pg) in zip(me.named_parameters(), mg.named_parameters()):
+            assert torch.equal(pe, pg), (tag, n)
+    # not vacuous: the G replays moved the weights the D graph reads between its capture and its last replay
+    assert any(not torch.equal(a, c) for a, c in zip(at_d_capture, at_last_d))

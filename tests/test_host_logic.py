@@ -541,3 +541,97 @@ def test_winograd_f23_row_algebra_of_conv_wino_hip():
 
     assert float((wino(x, False) - F.conv2d(x, wt, padding=1)).abs().max()) < 1e-12
     assert float((wino(x, True) - F.conv2d((x - mu) * rs, wt, padding=1)).abs().max()) < 1e-11
+
+
+def test_captured_train_steps_repack_every_module_another_step_trains(monkeypatch):
+    """graphed_d_step / graphed_g_step: the body drops, BEFORE anything reads them, the weight packs of exactly the net's modules
+    that own a trained parameter (the G step trains the net between D replays, and the other way round for D) -- so the capture
+    records the re-pack kernels instead of baking in packs of an eager step that go stale and are freed by the next eager consumer.
+    Frozen modules keep their packs (no re-pack kernels in every replay), lifetime buffers (_e4s_bufs) and the style plan survive.
+    CPU stand-ins for the networks; GraphedStep replaced by a stub that runs the body once (the capture is GPU-side)."""
+    from e4s_amd import optim, packs
+    from e4s_amd.train import TrainIteration
+
+    def dress(m):                                          # every kind of cached pack, as the real modules hold them
+        for name in packs.PACK_ATTRS:
+            setattr(m, name, ("key", "old"))
+        m.__dict__["_e4s_bufs"] = {"w": "lifetime"}
+        m._e4s_style_plan = {"key": "addresses"}
+        return m
+
+    class Leaf(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.weight = torch.nn.Parameter(torch.ones(1))
+
+    class Net(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.enc = dress(torch.nn.Sequential(dress(Leaf()), dress(Leaf())))      # trained
+            self.mlp = dress(Leaf())                                                 # trained (its stacked pack lives on the Net)
+            self.G = dress(torch.nn.Sequential(dress(Leaf()), dress(Leaf())))        # G[0] trained, G[1] frozen
+            self.style = dress(torch.nn.Sequential(dress(Leaf())))                   # frozen
+            dress(self)
+            self.seen = []
+
+        def forward(self, img, onehot, **kw):
+            self.seen.append({n: getattr(m, "_e4s_pack") for n, m in self.named_modules()})
+            return img * self.enc[0].weight * self.enc[1].weight * self.mlp.weight * self.G[0].weight, None
+
+    class Disc(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.lin = torch.nn.Linear(3 * 4 * 4, 1)
+
+        def forward(self, x):
+            return self.lin(x.flatten(1) ** 2)
+    calls = []
+
+    class Stub:
+        def __init__(self, opt, body, warmup=2, also_written=()):
+            calls.append(opt)
+            body()
+    monkeypatch.setattr(optim, "GraphedStep", Stub)
+    net, disc = Net(), Disc()
+    for p in list(net.G[1].parameters()) + list(net.style.parameters()):
+        p.requires_grad = False
+    trained = {"", "enc", "enc.0", "enc.1", "mlp", "G", "G.0"}
+    frozen = {"G.1", "style", "style.0"}
+    assert {n for n, _ in net.named_modules()} == trained | frozen
+    it = TrainIteration(net, disc, {}, torch.optim.SGD([p for p in net.parameters() if p.requires_grad], lr=1e-3),
+                        torch.optim.SGD(disc.parameters(), lr=1e-3))
+    img = torch.rand(2, 3, 4, 4)
+    for step in ("d", "g"):
+        for _, m in net.named_modules():
+            dress(m)
+        net.seen.clear()
+        if step == "d":
+            it.graphed_d_step(img, None)
+        else:
+            it.graphed_g_step(img, None)
+        assert calls[-1] is (it.opt_d if step == "d" else it.opt)
+        assert len(net.seen) == 1
+        for n, m in net.named_modules():
+            assert net.seen[0][n] == (None if n in trained else ("key", "old")), (step, n)        # dropped before the forward read it
+            for name in packs.PACK_ATTRS:
+                assert getattr(m, name) == (None if n in trained else ("key", "old")), (step, n, name)
+            assert m._e4s_bufs == {"w": "lifetime"} and m._e4s_style_plan == {"key": "addresses"}, (step, n)
+
+
+def test_every_module_cache_of_the_package_is_a_listed_pack_or_a_known_non_pack():
+    """packs.invalidate_module_packs drops the attributes listed in packs.PACK_ATTRS; a cache added under another name would escape it
+    and a captured train step would serve it stale.  Every `._e4s_*` / `._*pack*` attribute the package assigns is listed, or is one
+    of the caches that must survive (lifetime buffers, address-keyed job tables, a structural check)."""
+    from e4s_amd import packs
+    keep = {"_e4s_bufs", "_e4s_style_plan", "_e4s_style_ok"}
+    pkg = os.path.join(ROOT, "e4s_amd")
+    found = set()
+    for dirpath, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py"):
+                src = open(os.path.join(dirpath, f)).read()
+                found |= set(re.findall(r"\.(_e4s_\w+|_\w*pack\w*)\s*=[^=]", src))
+                found |= set(re.findall(r"setdefault\(\"(_e4s_\w+)\"", src))
+    assert "_e4s_pack" in found and "_mlp_pack" in found and "_e4s_bufs" in found
+    assert found - keep <= set(packs.PACK_ATTRS), sorted(found - keep - set(packs.PACK_ATTRS))
+    assert not keep & set(packs.PACK_ATTRS)
