@@ -1472,3 +1472,91 @@ def cosine_bwd(a, b, coef, gout, gmul, da_acc=None):
     call("e4s_cosine_bwd_f32", fptr(a), fptr(b), fptr(coef), fptr(gout), float(gmul), fptr(da), n, d,
          1 if da_acc is not None else 0, stream())
     return da
+
+
+# ---- BiSeNet face parser (face_parser.py) ---------------------------------------------------
+def parser_preprocess(src, taps):
+    """uint8 NHWC [B,H,W,3] or fp32 NCHW [B,3,H,W] in [0,1] -> the parser's input NHWC [B,H/2,W/2,3]: bicubic /2 (reflect),
+    clamp(0,1), ImageNet normalisation.  taps: the 8 host-side filter taps (a sequence of floats)."""
+    if src.dtype == torch.uint8:
+        b, h, w, c = src.shape
+        is_u8 = 1
+    else:
+        src = _f32(src)
+        b, c, h, w = src.shape
+        is_u8 = 0
+    if c != 3:
+        raise RuntimeError(f"parser_preprocess: 3-channel images, got shape {tuple(src.shape)}")
+    y = torch.empty(b, h // 2, w // 2, 3, device=src.device, dtype=torch.float32)
+    k = (ctypes.c_float * 8)(*[float(t) for t in taps])
+    call("e4s_parser_preprocess_f32", ptr(src.contiguous()), is_u8, fptr(y), b, h, w, k, stream())
+    return y
+
+
+def maxpool3s2p1(x):
+    """nn.MaxPool2d(3, 2, padding=1) of x NHWC."""
+    x = _f32(x)
+    b, hi, wi, c = x.shape
+    y = torch.empty(b, (hi - 1) // 2 + 1, (wi - 1) // 2 + 1, c, device=x.device, dtype=torch.float32)
+    call("e4s_maxpool3s2p1_f32", fptr(x), fptr(y), b, hi, wi, c, stream())
+    return y
+
+
+def add_relu(a, r=None, out=None, coff=0):
+    """relu(a + r) of NHWC maps (r None: relu(a)), into `out` (a wider NHWC map: channels coff .. coff+C) when given."""
+    a = _f32(a)
+    c = a.shape[-1]
+    npix = a.numel() // c
+    if out is None:
+        out = torch.empty_like(a)
+    elif tuple(out.shape[:-1]) != tuple(a.shape[:-1]) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise RuntimeError("add_relu(out=...): a contiguous fp32 NHWC map with the pixels of a")
+    call("e4s_add_relu_f32", fptr(a), fptr(_f32(r)) if r is not None else None, fptr(out), npix, c, out.shape[-1], coff, stream())
+    return out
+
+
+def mean_hw(x):
+    """x NHWC [B,H,W,C] -> [B,C] spatial mean."""
+    x = _f32(x)
+    b, c = x.shape[0], x.shape[-1]
+    out = torch.empty(b, c, device=x.device, dtype=torch.float32)
+    call("e4s_mean_hw_f32", fptr(x), fptr(out), b, x.numel() // (b * c), c, stream())
+    return out
+
+
+def parser_fc(v, w, bias, act=0, offset=0.0):
+    """act(v @ w.T + bias) + offset on [B,Ci] (w [Co,Ci], or None: identity); act 0 none, 1 ReLU, 2 sigmoid."""
+    v = _f32(v)
+    b, ci = v.shape
+    co = w.shape[0] if w is not None else ci
+    out = torch.empty(b, co, device=v.device, dtype=torch.float32)
+    call("e4s_parser_fc_f32", fptr(v), fptr(_f32(w)) if w is not None else None, fptr(_f32(bias)) if bias is not None else None,
+         fptr(out), b, ci, co, int(act), float(offset), stream())
+    return out
+
+
+def gate_add_up2(x, gate, add):
+    """nearest x2 of (x * gate[:, None, None] + add): x NHWC [B,h,w,C], gate [B,C], add [B,C] or NHWC [B,h,w,C]."""
+    x = _f32(x)
+    b, h, w, c = x.shape
+    add = _f32(add)
+    add_map = 1 if add.dim() == 4 else 0
+    if tuple(add.shape) != ((b, h, w, c) if add_map else (b, c)) or tuple(gate.shape) != (b, c):
+        raise RuntimeError("gate_add_up2: gate [B,C], add [B,C] or [B,h,w,C]")
+    y = torch.empty(b, 2 * h, 2 * w, c, device=x.device, dtype=torch.float32)
+    call("e4s_gate_add_up2_f32", fptr(x), fptr(_f32(gate)), fptr(add), add_map, fptr(y), b, h, w, c, stream())
+    return y
+
+
+def parser_head(logits, ncls, size, seg12=False, labels=True, onehot=False, nchw=False):
+    """Bilinear (align_corners=True) upsampling of NHWC logits [B,h,w,>=ncls] to size (H, W) + first-maximum argmax.
+    Returns (labels uint8 [B,H,W] | None, one-hot fp32 [B,12|ncls,H,W] | None, logits NCHW [B,ncls,H,W] | None)."""
+    logits = _f32(logits)
+    b, h, w, cs = logits.shape
+    hh, ww = size
+    dev = logits.device
+    lab = torch.empty(b, hh, ww, device=dev, dtype=torch.uint8) if labels else None
+    oh = torch.empty(b, 12 if seg12 else ncls, hh, ww, device=dev, dtype=torch.float32) if onehot else None
+    nc = torch.empty(b, ncls, hh, ww, device=dev, dtype=torch.float32) if nchw else None
+    call("e4s_parser_head_f32", fptr(logits), b, h, w, ncls, cs, hh, ww, 1 if seg12 else 0, ptr(lab), fptr(oh), fptr(nc), stream())
+    return lab, oh, nc

@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E4S_LIB_PATH") or os.path.join(_HERE, "libe4s_hip.so")      # (E4S_LIB_PATH: A/B runs of two builds)
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -206,6 +206,13 @@ SIGNATURES = {
     "e4s_cosine_f32": [c_p, c_p, c_p, c_p, c_i, c_l, c_p],
     "e4s_cosine_ws_doubles": [c_i, c_l],
     "e4s_cosine_bwd_f32": [c_p, c_p, c_p, c_p, c_f, c_p, c_i, c_l, c_i, c_p],
+    "e4s_parser_preprocess_f32": [c_p, c_i, c_p, c_i, c_i, c_i, ctypes.POINTER(c_f), c_p],
+    "e4s_maxpool3s2p1_f32": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
+    "e4s_add_relu_f32": [c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_p],
+    "e4s_mean_hw_f32": [c_p, c_p, c_i, c_i, c_i, c_p],
+    "e4s_parser_fc_f32": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p],
+    "e4s_gate_add_up2_f32": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p],
+    "e4s_parser_head_f32": [c_p] + [c_i] * 8 + [c_p, c_p, c_p, c_p],
 }
 
 INT64_RETURN = {"e4s_split16_bytes", "e4s_instnorm_ws_doubles", "e4s_conv_bwd_ws_floats", "e4s_grouped_linear_t_ws_floats", "e4s_reduce_parts_ws_floats", "e4s_instnorm_bwd_ws_doubles", "e4s_prelu_bwd_ws_floats", "e4s_conv_wgrad_ws_floats", "e4s_conv_bf16x3_ws_floats", "e4s_conv_region_ws_floats", "e4s_lpips_layer_ws_doubles", "e4s_conv_mfma_ws_floats",

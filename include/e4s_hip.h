@@ -632,6 +632,33 @@ int64_t e4s_cosine_ws_doubles(int B, int64_t D);
 int e4s_cosine_bwd_f32(const float* a, const float* b, const float* coef, const float* gout, float gmul, float* da, int B,
                        int64_t D, int accumulate, void* stream);
 
+/* ---- BiSeNet face parser (ABI v15; e4s_amd/face_parser.py, src/pretrained/face_parsing/) ------------------------------ */
+/* BicubicDownSample(factor 2) + clamp(0, 1) + ImageNet (x - mean) / std in one pass (face_parsing_demo.py:15-73,152-156):
+ * src uint8 NHWC [B,H,W,3] (is_u8 = 1; decoded pixels, read as x / 255) or fp32 NCHW [B,3,H,W] in [0,1]; dst fp32 NHWC
+ * [B,H/2,W/2,3].  taps8: the 8 normalised filter taps (HOST memory, passed by value).  Reflect padding 3/3, H and W even. */
+int e4s_parser_preprocess_f32(const void* src, int is_u8, float* dst, int B, int H, int W, const float* taps8, void* stream);
+/* nn.MaxPool2d(3, 2, padding=1): x NHWC [B,Hi,Wi,C] -> y [B,(Hi-1)/2+1,(Wi-1)/2+1,C]; C % 4 == 0 */
+int e4s_maxpool3s2p1_f32(const float* x, float* y, int B, int Hi, int Wi, int C, void* stream);
+/* y[p, y_coff + c] = relu(a[p, c] + r[p, c]) for npix pixels of C channels (r NULL: relu(a)); y has y_cstride channels per
+ * pixel (0 = C).  The residual epilogue of a ResNet BasicBlock, and a copy into a channel slice of a wider map. */
+int e4s_add_relu_f32(const float* a, const float* r, float* y, int64_t npix, int C, int y_cstride, int y_coff, void* stream);
+/* out[b, c] = mean over HW of x NHWC [B,HW,C] (fixed summation order) */
+int e4s_mean_hw_f32(const float* x, float* out, int B, int HW, int C, void* stream);
+/* out[b, o] = act(sum_i w[o, i] v[b, i] + bias[o]) + offset; act 0 none, 1 ReLU, 2 sigmoid; w [Co][Ci] or NULL (identity,
+ * Ci == Co); bias may be NULL */
+int e4s_parser_fc_f32(const float* v, const float* w, const float* bias, float* out, int B, int Ci, int Co, int act, float offset,
+                      void* stream);
+/* nearest x2 of (x * gate + add): x NHWC [B,h,w,C], gate [B,C], add [B,C] (add_map = 0) or [B,h,w,C] (add_map = 1)
+ * -> y [B,2h,2w,C]; C % 4 == 0 */
+int e4s_gate_add_up2_f32(const float* x, const float* gate, const float* add, int add_map, float* y, int B, int h, int w, int C,
+                         void* stream);
+/* F.interpolate(bilinear, align_corners=True) of NHWC logits [B,h,w,cstride] (the first ncls <= 32 channels) to HxW, then
+ * the first maximum over classes (torch.argmax).  Outputs (each may be NULL): labels uint8 [B,H,W] (mapped to the 12 E4S
+ * classes when seg12 = 1, which needs ncls == 19), onehot fp32 [B,12 or ncls,H,W] of those labels, nchw fp32 [B,ncls,H,W]
+ * the upsampled logits. */
+int e4s_parser_head_f32(const float* logits, int B, int h, int w, int ncls, int cstride, int H, int W, int seg12,
+                        uint8_t* labels, float* onehot, float* nchw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
