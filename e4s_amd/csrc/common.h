@@ -23,6 +23,35 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// wave64 sums of N values per lane at once (N a power of two <= 64): a butterfly that halves the set at every step -- the lane keeps
+// the half its lane bit selects and adds the partner's copy of it -- then finishes the single survivor like wave_sum.  N - 1 + (6 -
+// log2 N) shuffles in place of 6 N.  Afterwards v[0] is the complete sum of value (lane >> (6 - log2 N)), on every lane of that group.
+// Each value goes through wave_sum's additions (offsets 32, 16, ..., 1; a + b == b + a), so it has wave_sum's bits.
+template <int N, int CNT, int O>
+__device__ __forceinline__ void packed_wave_sum_step(float (&v)[N], const int lane) {      // every index a compile-time constant
+    if constexpr (O > 0) {
+        if constexpr (CNT > 1) {
+            constexpr int H = CNT / 2;
+            const bool up = lane & O;
+#pragma unroll
+            for (int i = 0; i < H; ++i) {
+                const float keep = up ? v[i + H] : v[i], send = up ? v[i] : v[i + H];
+                v[i] = keep + __shfl_xor(send, O, 64);
+            }
+            packed_wave_sum_step<N, H, O / 2>(v, lane);
+        } else {
+            v[0] += __shfl_xor(v[0], O, 64);
+            packed_wave_sum_step<N, 1, O / 2>(v, lane);
+        }
+    }
+}
+
+template <int N>
+__device__ __forceinline__ void packed_wave_sum(float (&v)[N], const int lane) {
+    static_assert(N >= 1 && N <= 64 && (N & (N - 1)) == 0, "N: a power of two <= 64");
+    packed_wave_sum_step<N, N, 32>(v, lane);
+}
+
 // 4x4 transpose inside each quad of lanes (two DPP quad_perm exchanges): in: a_i = M[i][lane & 3]; out: a_k = M[lane & 3][k].
 // MFMA 32x32 accumulators hold one COLUMN per lane and rows (r & 3) + 8 (r >> 2) + 4 kh in register r: transposing registers
 // 4g .. 4g+3 across the quad gives each lane four consecutive columns of ONE row -- a 16-byte NHWC store instead of four 4-byte

@@ -454,42 +454,52 @@ __device__ __forceinline__ int nearest_src(int dst, int in, int out) {
     return s < in - 1 ? s : in - 1;
 }
 
-// ---- regional average pooling: block = (b, 64-channel slab); each thread owns one channel for a
-// quarter of the pixels and keeps R running sums in LDS columns it alone touches ------------------
-__global__ void region_mean_kernel(const float* __restrict__ feats, const uint8_t* __restrict__ labels, int Hm, int Wm,
-                                   float* __restrict__ out, int H, int W, int C, int R, int out_stride, int out_off) {
-    extern __shared__ float sm[];          // sums[NPG][R][64], cnt[R]
-    constexpr int NPG = 16;                // pixel groups per block (1024 threads)
+// ---- regional average pooling, two stages.  Stage 1: block = (sample, 64-channel slab, range of RM_PIX pixels); 16 lanes x float4
+// walk the slab's 64 channels, 16 pixel groups, and every thread keeps R running float4 sums in LDS columns it alone touches.  The
+// block adds its 16 pixel groups in order and writes one partial [R][64] (+ the R pixel counts) to the workspace.  Stage 2 adds the
+// partials of a (sample, region, channel) in split order and divides: no float atomics, and the split (RM_PIX pixels per block) is
+// a function of the map alone, so a sample's means do not depend on the batch it sits in.  A map of <= RM_PIX pixels is one block per
+// (sample, slab), which writes the means itself.  (One block per (sample, slab) for the whole map -- 64 blocks on 256 CUs at the
+// 256-channel 64^2 level -- read that level's 67 MB at 0.5 TB/s.)
+constexpr int RM_PIX = 256;                // pixels per stage-1 block
+constexpr int RM_NPG = 16;                 // pixel groups per block (256 threads)
+__global__ __launch_bounds__(256) void region_mean_kernel(const float* __restrict__ feats, const uint8_t* __restrict__ labels, int Hm,
+                                                          int Wm, float* __restrict__ out, float* __restrict__ ws, int H, int W, int C,
+                                                          int R, int out_stride, int out_off, int nsplit) {
+    extern __shared__ float sm[];          // sums[RM_NPG][R][64], cnt[R]
     const int slabs = C / 64;
-    const int b = blockIdx.x / slabs, slab = blockIdx.x % slabs;
-    const int cl = threadIdx.x & 63, pg = threadIdx.x >> 6;
+    const int split = blockIdx.x % nsplit;
+    const int slab = (blockIdx.x / nsplit) % slabs;
+    const int b = blockIdx.x / (nsplit * slabs);
+    const int cl = (threadIdx.x & 15) * 4, pg = threadIdx.x >> 4;
     float* sums = sm;
-    int* cnt = reinterpret_cast<int*>(sm + NPG * R * 64);
-    for (int t = threadIdx.x; t < NPG * R * 64; t += blockDim.x) sums[t] = 0.f;
+    int* cnt = reinterpret_cast<int*>(sm + RM_NPG * R * 64);
+    for (int t = threadIdx.x; t < RM_NPG * R * 64; t += blockDim.x) sums[t] = 0.f;
     for (int t = threadIdx.x; t < R; t += blockDim.x) cnt[t] = 0;
     __syncthreads();
     const int HW = H * W;
+    const int pbeg = split * RM_PIX, pend = pbeg + RM_PIX < HW ? pbeg + RM_PIX : HW;
     const float* fb = feats + (int64_t)b * HW * C + slab * 64 + cl;
     float* mine = sums + (pg * R) * 64 + cl;
-    // eight pixels in flight per thread (feature + label loads first, then the LDS sums in pixel order: the same additions in the same order; the
-    // one-load-per-dependent-add loop read the 134 MB of a 512-channel 64^2 level at 0.96 TB/s)
+    // eight pixels in flight per thread (feature + label loads first, then the LDS sums in pixel order)
     constexpr int U = 8;
-    for (int p0 = pg; p0 < HW; p0 += NPG * U) {
-        float v[U];
+    for (int p0 = pbeg + pg; p0 < pend; p0 += RM_NPG * U) {
+        f32x4 v[U];
         int lab[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int p = p0 + u * NPG;
-            const bool ok = p < HW;
-            const int pp = ok ? p : 0;
+            const int p = p0 + u * RM_NPG;
+            const bool ok = p < pend;
+            const int pp = ok ? p : pbeg;
             const int yy = pp / W, xx = pp - yy * W;
             lab[u] = ok ? labels[((int64_t)b * Hm + nearest_src(yy, Hm, H)) * Wm + nearest_src(xx, Wm, W)] : -1;
-            v[u] = ok ? fb[(int64_t)pp * C] : 0.f;
+            v[u] = *reinterpret_cast<const f32x4*>(fb + (int64_t)pp * C);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            if (lab[u] >= 0) {
-                mine[lab[u] * 64] += v[u];
+            if (lab[u] >= 0 && lab[u] < R) {
+                f32x4* acc = reinterpret_cast<f32x4*>(mine + lab[u] * 64);
+                *acc += v[u];
                 if (cl == 0) atomicAdd(&cnt[lab[u]], 1);
             }
         }
@@ -498,10 +508,32 @@ __global__ void region_mean_kernel(const float* __restrict__ feats, const uint8_
     for (int t = threadIdx.x; t < R * 64; t += blockDim.x) {
         const int r = t / 64, c = t % 64;
         float s = 0.f;
-        for (int j = 0; j < NPG; ++j) s += sums[(j * R + r) * 64 + c];
-        const int n = cnt[r];
-        out[((int64_t)b * R + r) * out_stride + out_off + slab * 64 + c] = n > 0 ? s / (float)n : 0.f;
+        for (int j = 0; j < RM_NPG; ++j) s += sums[(j * R + r) * 64 + c];
+        if (ws) {
+            ws[((int64_t)blockIdx.x * R + r) * 65 + c] = s;
+            if (c == 0) ws[((int64_t)blockIdx.x * R + r) * 65 + 64] = __int_as_float(cnt[r]);
+        } else {
+            const int n = cnt[r];
+            out[((int64_t)b * R + r) * out_stride + out_off + slab * 64 + c] = n > 0 ? s / (float)n : 0.f;
+        }
     }
+}
+
+// stage 2: thread = (sample, region, channel); the nsplit partials (and counts) added in split order
+__global__ void region_mean_finish_kernel(const float* __restrict__ ws, float* __restrict__ out, int B, int C, int R, int out_stride,
+                                          int out_off, int nsplit) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * R * C) return;
+    const int c = i % C, r = (i / C) % R, b = i / (C * R);
+    const int slab = c >> 6, cc = c & 63;
+    const float* p = ws + (((int64_t)(b * (C / 64) + slab) * nsplit) * R + r) * 65;
+    float s = 0.f;
+    int n = 0;
+    for (int k = 0; k < nsplit; ++k) {
+        s += p[(int64_t)k * R * 65 + cc];
+        n += __float_as_int(p[(int64_t)k * R * 65 + 64]);
+    }
+    out[((int64_t)b * R + r) * out_stride + out_off + c] = n > 0 ? s / (float)n : 0.f;
 }
 
 // ---- LocalMLP layer: one wave per (r, o) output neuron, all B samples at once; the weight row is
@@ -542,6 +574,74 @@ __global__ void grouped_linear_kernel(const float* __restrict__ x, const float* 
             a = a * scale + bs;
             if (act == 1) a = a > 0.f ? a : a * alpha;
             y[((int64_t)b * R + r) * O + o] = a + ad;
+        }
+    }
+}
+
+// Small K (<= 256 * KV floats, KV <= 6) on a big table of rows: one wave per NR consecutive output rows of a region.  The NR weight rows
+// (NR * KV float4 per lane) are read once into registers; the samples go in chunks of GL_TB, each sample's input row is loaded once
+// and feeds NR accumulators, and the NR * GL_TB per-lane sums are reduced TOGETHER (packed_wave_sum: NR * GL_TB - 1 shuffles in place
+// of 6 per value, the additions of wave_sum).  The per-lane products are explicit FMAs in element order, so a sample's outputs do not
+// depend on the slot (hence the batch) it is computed in.  At K = 512 that kernel held 2 of its 16 weight registers per wave and paid B serial dot products
+// with a wave reduction each per 2 KB of weights: 163 MB in 134 us.
+constexpr int GL_TB = 8;
+template <int KV, int NR>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void grouped_linear_rows_kernel(const float* __restrict__ x, const float* __restrict__ Wt,
+                                                                  const float* __restrict__ bias, const float* __restrict__ add,
+                                                                  float* __restrict__ y, int B, int R, int K, int O, float scale,
+                                                                  int act, float alpha) {
+    constexpr int N = NR * GL_TB;                     // values per lane in the packed reduction (a power of two <= 64)
+    const int lane = threadIdx.x & 63;
+    const int opr = O / NR;                           // waves per region
+    const int64_t wid = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (wid >= (int64_t)R * opr) return;
+    const int r = (int)(wid / opr), o0 = (int)(wid % opr) * NR;
+    const float* wrow = Wt + ((int64_t)r * O + o0) * K;
+    f32x4 w[NR][KV];
+#pragma unroll
+    for (int n = 0; n < NR; ++n)
+#pragma unroll
+        for (int j = 0; j < KV; ++j) {
+            const int i = (j * 64 + lane) * 4;
+            w[n][j] = i < K ? *reinterpret_cast<const f32x4*>(wrow + (int64_t)n * K + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    // after the packed butterfly the lane holds value (lane >> SH) = tb * NR + n, complete on every lane of its group of 1 << SH
+    static_assert(N == 64 || N == 32, "lane -> value mapping below");
+    constexpr int SH = N == 64 ? 0 : 1;
+    const int mine = lane >> SH, tbm = mine / NR, nm = mine % NR;
+    const float bs = bias ? bias[(int64_t)r * O + o0 + nm] : 0.f;
+    const float ad = add ? add[o0 + nm] : 0.f;
+    for (int b0 = 0; b0 < B; b0 += GL_TB) {
+        float v[N];
+#pragma unroll
+        for (int tb = 0; tb < GL_TB; ++tb) {
+            if (b0 + tb < B) {                        // wave-uniform
+                const float* xr = x + ((int64_t)(b0 + tb) * R + r) * K;
+                f32x4 xv[KV];
+#pragma unroll
+                for (int j = 0; j < KV; ++j) {
+                    const int i = (j * 64 + lane) * 4;
+                    xv[j] = i < K ? *reinterpret_cast<const f32x4*>(xr + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+#pragma unroll
+                for (int n = 0; n < NR; ++n) {
+                    float acc = 0.f;
+#pragma unroll
+                    for (int j = 0; j < KV; ++j)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) acc = fmaf(w[n][j][e], xv[j][e], acc);      // spelled out: every (sample slot, row)
+                    v[tb * NR + n] = acc;                                                       // instance rounds alike
+                }
+            } else {
+#pragma unroll
+                for (int n = 0; n < NR; ++n) v[tb * NR + n] = 0.f;
+            }
+        }
+        packed_wave_sum<N>(v, lane);
+        if ((lane & ((1 << SH) - 1)) == 0 && b0 + tbm < B) {
+            float a = v[0] * scale + bs;
+            if (act == 1) a = a > 0.f ? a : a * alpha;
+            y[((int64_t)(b0 + tbm) * R + r) * O + o0 + nm] = a + ad;
         }
     }
 }
@@ -719,12 +819,32 @@ extern "C" int e4s_instnorm_finalize_se_f32(const double* ws, float* stats, cons
     return 0;
 }
 
-extern "C" int e4s_region_mean_f32(const float* feats, const uint8_t* labels, int Hm, int Wm, float* out, int B, int H,
+static int region_mean_nsplit(int HW) { return (HW + RM_PIX - 1) / RM_PIX; }
+
+extern "C" int64_t e4s_region_mean_ws_floats(int B, int HW, int C, int R) {
+    const int ns = region_mean_nsplit(HW);
+    return ns > 1 ? (int64_t)B * (C / 64) * ns * R * 65 : 0;
+}
+
+extern "C" int e4s_region_mean_f32(const float* feats, const uint8_t* labels, int Hm, int Wm, float* out, float* ws, int B, int H,
                                    int W, int C, int R, int out_stride, int out_off, void* stream) {
-    if (C % 64 || R > 64) return (int)hipErrorInvalidValue;
-    const size_t smem = (size_t)(16 * R * 64) * sizeof(float) + (size_t)R * sizeof(int);
-    hipLaunchKernelGGL(region_mean_kernel, dim3(B * (C / 64)), dim3(1024), smem, as_stream(stream), feats, labels, Hm, Wm, out, H, W, C, R, out_stride, out_off);
+    if (C % 64 || R > 64 || R < 1 || B <= 0 || H <= 0 || W <= 0) return (int)hipErrorInvalidValue;
+    if (reinterpret_cast<uintptr_t>(feats) & 15) return (int)hipErrorInvalidValue;          // 16-byte loads along the channels
+    const int ns = region_mean_nsplit(H * W);
+    if (ns > 1 && !ws) return (int)hipErrorInvalidValue;
+    const int64_t blocks = (int64_t)B * (C / 64) * ns;
+    if (blocks >= (1ll << 31) || (int64_t)B * R * C >= (1ll << 31)) return (int)hipErrorInvalidValue;
+    const size_t smem = (size_t)(RM_NPG * R * 64) * sizeof(float) + (size_t)R * sizeof(int);
+    if (smem > 64 * 1024) return (int)hipErrorInvalidValue;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(region_mean_kernel, dim3((unsigned)blocks), dim3(256), smem, st, feats, labels, Hm, Wm, out, ns > 1 ? ws : nullptr,
+                       H, W, C, R, out_stride, out_off, ns);
     E4S_CHECK_LAUNCH();
+    if (ns > 1) {
+        const int n = B * R * C;
+        hipLaunchKernelGGL(region_mean_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ws, out, B, C, R, out_stride, out_off, ns);
+        E4S_CHECK_LAUNCH();
+    }
     return 0;
 }
 
@@ -733,12 +853,25 @@ extern "C" int e4s_grouped_linear_f32(const float* x, const float* W, const floa
     if (K % 4) return (int)hipErrorInvalidValue;
     const int64_t nw = (int64_t)R * O;
     if (nw <= 0 || B <= 0) return 0;
+    hipStream_t st = as_stream(stream);
     if (K > 64 * 4 * MAXKV) {
-        hipLaunchKernelGGL(grouped_linear_longk_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, as_stream(stream), x, W, bias, add, y, B, R, K, O, scale, act, alpha);
+        hipLaunchKernelGGL(grouped_linear_longk_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, st, x, W, bias, add, y, B, R, K, O, scale, act, alpha);
         E4S_CHECK_LAUNCH();
         return 0;
     }
-    hipLaunchKernelGGL(grouped_linear_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, as_stream(stream), x, W, bias, add, y, B, R, K, O, scale, act, alpha);
+    // several rows per wave once the rows alone fill the chip (a policy of the layer's shape, never of the batch); the small tables
+    // (style MLP, SE gates: a few hundred rows) keep a wave per row
+    if (K <= 1536 && O % 8 == 0 && nw >= 4096) {
+        if (K <= 512)
+            hipLaunchKernelGGL((grouped_linear_rows_kernel<2, 8>), dim3((unsigned)((nw / 8 + 3) / 4)), dim3(256), 0, st, x, W, bias, add, y, B, R, K, O, scale, act, alpha);
+        else if (K <= 1024)
+            hipLaunchKernelGGL((grouped_linear_rows_kernel<4, 4>), dim3((unsigned)((nw / 4 + 3) / 4)), dim3(256), 0, st, x, W, bias, add, y, B, R, K, O, scale, act, alpha);
+        else
+            hipLaunchKernelGGL((grouped_linear_rows_kernel<6, 4>), dim3((unsigned)((nw / 4 + 3) / 4)), dim3(256), 0, st, x, W, bias, add, y, B, R, K, O, scale, act, alpha);
+        E4S_CHECK_LAUNCH();
+        return 0;
+    }
+    hipLaunchKernelGGL(grouped_linear_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, st, x, W, bias, add, y, B, R, K, O, scale, act, alpha);
     E4S_CHECK_LAUNCH();
     return 0;
 }

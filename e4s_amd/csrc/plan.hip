@@ -27,6 +27,33 @@ __global__ void mask_labels_kernel(const float* __restrict__ mask, uint8_t* __re
     if (!clean || ones != 1) atomicOr(flags, 1);
 }
 
+// HW % 4 == 0: thread = 4 consecutive pixels, one 16-byte load per region plane (four planes in flight) and one 4-byte label store;
+// per pixel the comparisons of the kernel above in the same order (first maximum wins).  The 4-byte-per-lane form read the 201 MB of a
+// batch of 16 one-hot 512^2 masks at 2.7 TB/s.
+__global__ __launch_bounds__(256) void mask_labels_vec4_kernel(const float* __restrict__ mask, uint8_t* __restrict__ labels, int* flags,
+                                                               int B, int R, int64_t HW) {
+    const int64_t HW4 = HW >> 2;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)B * HW4) return;
+    const int64_t b = i / HW4, p = (i - b * HW4) * 4;
+    const float* m = mask + b * R * HW + p;
+    f32x4 best = *reinterpret_cast<const f32x4*>(m);
+    int arg[4] = {0, 0, 0, 0}, ones[4] = {0, 0, 0, 0};
+    bool clean = true;
+#pragma unroll 4
+    for (int r = 0; r < R; ++r) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(m + (int64_t)r * HW);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (v[e] > best[e]) { best[e] = v[e]; arg[e] = r; }
+            if (v[e] == 1.f) ++ones[e];
+            else if (v[e] != 0.f) clean = false;
+        }
+    }
+    *reinterpret_cast<uint32_t*>(labels + b * HW + p) = (uint32_t)arg[0] | ((uint32_t)arg[1] << 8) | ((uint32_t)arg[2] << 16) | ((uint32_t)arg[3] << 24);
+    if (!clean || ones[0] != 1 || ones[1] != 1 || ones[2] != 1 || ones[3] != 1) atomicOr(flags, 1);
+}
+
 // legacy 'nearest' source index (F.interpolate(mode='nearest')): min(floor(dst * in/out), in-1)
 __device__ __forceinline__ int nearest_src(int dst, int in, int out) {
     const float scale = (float)in / (float)out;
@@ -140,8 +167,15 @@ __global__ void plan_scatter_kernel(PlanGeom g, const uint8_t* __restrict__ labe
 extern "C" int e4s_mask_labels(const float* mask, uint8_t* labels, int* flags, int B, int R, int Hm, int Wm, void* stream) {
     const int64_t n = (int64_t)B * Hm * Wm;
     if (n <= 0 || R <= 0 || R > 255) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(mask_labels_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), mask,
-                       labels, flags, B, R, (int64_t)Hm * Wm);
+    const int64_t HW = (int64_t)Hm * Wm;
+    if (n >= (1ll << 39)) return (int)hipErrorInvalidValue;
+    // 16-byte loads need every plane (and the label row) 16- / 4-byte aligned: HW % 4 == 0 on bases that are
+    if (HW % 4 == 0 && (reinterpret_cast<uintptr_t>(mask) & 15) == 0 && (reinterpret_cast<uintptr_t>(labels) & 3) == 0)
+        hipLaunchKernelGGL(mask_labels_vec4_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, as_stream(stream), mask,
+                           labels, flags, B, R, HW);
+    else
+        hipLaunchKernelGGL(mask_labels_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), mask,
+                           labels, flags, B, R, HW);
     E4S_CHECK_LAUNCH();
     return 0;
 }

@@ -66,11 +66,9 @@ __global__ void rowdot_multi_kernel(const e4s_rowdot_job* __restrict__ jobs, con
     float* out = out_base + jb.out_off;
     const int G = jb.G, O = jb.O, K = jb.K;
     const float scale = jb.scale;
-    float acc[RD_OW][GCHUNK];
+    float acc[RD_OW * GCHUNK];                     // [w][j]
 #pragma unroll
-    for (int w = 0; w < RD_OW; ++w)
-#pragma unroll
-        for (int j = 0; j < GCHUNK; ++j) acc[w][j] = 0.f;
+    for (int t = 0; t < RD_OW * GCHUNK; ++t) acc[t] = 0.f;
     for (int i = lane * 4; i < K; i += 256) {
         f32x4 m[RD_OW];
 #pragma unroll
@@ -82,26 +80,21 @@ __global__ void rowdot_multi_kernel(const e4s_rowdot_job* __restrict__ jobs, con
                 f32x4 x = *reinterpret_cast<const f32x4*>(in + (size_t)(g0 + j) * jb.in_stride + i);
                 if (MODE == 1) x *= x;
 #pragma unroll
-                for (int w = 0; w < RD_OW; ++w) acc[w][j] += m[w][0] * x[0] + m[w][1] * x[1] + m[w][2] * x[2] + m[w][3] * x[3];
+                for (int w = 0; w < RD_OW; ++w) acc[w * GCHUNK + j] += m[w][0] * x[0] + m[w][1] * x[1] + m[w][2] * x[2] + m[w][3] * x[3];
             }
         }
     }
-#pragma unroll
-    for (int w = 0; w < RD_OW; ++w) {
-        const int o = o0 + w;
-        if (o >= O) break;
-#pragma unroll
-        for (int j = 0; j < GCHUNK; ++j) {
-            if (g0 + j < G) {
-                const float a = wave_sum(acc[w][j]);
-                if (lane == 0) {
-                    float r;
-                    if (MODE == 0) r = a * scale + (jb.bias ? jb.bias[o] : 0.f);
-                    else r = scale * rsqrtf(scale * scale * a + 1e-8f);
-                    out[(size_t)(g0 + j) * O + o] = r;
-                }
-            }
-        }
+    // the 32 sums of the wave reduced together (32 shuffles; one wave_sum per sum was 192, more than the products cost): the additions
+    // are wave_sum's, so every output keeps its bits.  Lane 2t then holds sum t = w * GCHUNK + j.
+    static_assert(RD_OW * GCHUNK == 32, "lane -> (w, j) below");
+    packed_wave_sum<RD_OW * GCHUNK>(acc, lane);
+    const int o = o0 + (lane >> 1) / GCHUNK, g = g0 + (lane >> 1) % GCHUNK;
+    if ((lane & 1) == 0 && o < O && g < G) {
+        const float a = acc[0];
+        float r;
+        if (MODE == 0) r = a * scale + (jb.bias ? jb.bias[o] : 0.f);
+        else r = scale * rsqrtf(scale * scale * a + 1e-8f);
+        out[(size_t)g * O + o] = r;
     }
 }
 

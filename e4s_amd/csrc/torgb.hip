@@ -12,7 +12,8 @@ __device__ __forceinline__ int nearest_src(int dst, int in, int out) {
     return s < in - 1 ? s : in - 1;
 }
 
-// LP lanes cooperate on one pixel (each 4 channels per step); 64/LP pixels per wave step.
+// LP lanes cooperate on one pixel (each 4 channels per step); 64/LP pixels per wave step.  LP = 8 / 16 / 32 for Cin < 64 / < 128 / < 256;
+// Cin >= 256 (a whole wave per pixel) is torgb_wide_kernel below.
 template <int LP>
 __global__ void torgb_kernel(const float* __restrict__ x, const float* __restrict__ ws, const float* __restrict__ bias,
                              const float* __restrict__ skip, const float* __restrict__ k4,
@@ -76,6 +77,82 @@ __global__ void torgb_kernel(const float* __restrict__ x, const float* __restric
                 v += acc;
             }
             out[((int64_t)b * 3 + ch) * HW + rem] = v;
+        }
+    }
+}
+
+// Cin >= 256 (torgb_kernel<64>'s shapes): a wave takes TW_U consecutive pixels per step, 64 lanes x 16 B on each pixel's channels.  All
+// TW_U activation loads (and labels) are issued before the first product, and the 3 x TW_U per-lane sums are reduced together
+// (packed_wave_sum).  torgb_kernel<64> had ONE 1 KB load in flight per wave and 18 shuffles per pixel: 134 MB at 1.7 TB/s on the masked
+// 128^2 ToRGB of a batch of 8.  Per-lane products, their order and the reduction's additions are that kernel's: the same bits.
+constexpr int TW_U = 4;
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void torgb_wide_kernel(const float* __restrict__ x, const float* __restrict__ ws,
+                                                         const float* __restrict__ bias, const float* __restrict__ skip,
+                                                         const float* __restrict__ k4, const uint8_t* __restrict__ labels, int Hm, int Wm,
+                                                         int R, float* __restrict__ out, int B, int H, int W, int Cin) {
+    const int lane = threadIdx.x & 63;
+    const int64_t HW = (int64_t)H * W, npix = (int64_t)B * HW;
+    const int64_t wave_id = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    __shared__ float skf[16];
+    if (threadIdx.x < 16) skf[threadIdx.x] = k4 ? k4[15 - threadIdx.x] : 0.f;    // flipped (true convolution)
+    __syncthreads();
+    for (int64_t p0 = wave_id * TW_U; p0 < npix; p0 += nwaves * TW_U) {
+        float v[4 * TW_U];
+        const float* xp[TW_U];
+        const float* wp[TW_U];
+#pragma unroll
+        for (int u = 0; u < TW_U; ++u) {
+            const int64_t pp = p0 + u < npix ? p0 + u : p0;
+            const int b = (int)(pp / HW);
+            const int rem = (int)(pp - (int64_t)b * HW);
+            const int yy = rem / W, xx = rem - yy * W;
+            int g = b;
+            if (labels) g = b * R + labels[((int64_t)b * Hm + nearest_src(yy, Hm, H)) * Wm + nearest_src(xx, Wm, W)];
+            xp[u] = x + pp * Cin;
+            wp[u] = ws + (size_t)g * 3 * Cin;
+            v[4 * u] = v[4 * u + 1] = v[4 * u + 2] = v[4 * u + 3] = 0.f;
+        }
+        for (int c = lane * 4; c < Cin; c += 256) {
+            f32x4 xv[TW_U];
+#pragma unroll
+            for (int u = 0; u < TW_U; ++u) xv[u] = *reinterpret_cast<const f32x4*>(xp[u] + c);
+#pragma unroll
+            for (int u = 0; u < TW_U; ++u) {
+                const f32x4 w0 = *reinterpret_cast<const f32x4*>(wp[u] + c);
+                const f32x4 w1 = *reinterpret_cast<const f32x4*>(wp[u] + Cin + c);
+                const f32x4 w2 = *reinterpret_cast<const f32x4*>(wp[u] + 2 * Cin + c);
+                v[4 * u] += xv[u][0] * w0[0] + xv[u][1] * w0[1] + xv[u][2] * w0[2] + xv[u][3] * w0[3];
+                v[4 * u + 1] += xv[u][0] * w1[0] + xv[u][1] * w1[1] + xv[u][2] * w1[2] + xv[u][3] * w1[3];
+                v[4 * u + 2] += xv[u][0] * w2[0] + xv[u][1] * w2[1] + xv[u][2] * w2[2] + xv[u][3] * w2[3];
+            }
+        }
+        packed_wave_sum<4 * TW_U>(v, lane);           // lane holds value lane >> 2 = 4 u + ch
+        const int u = lane >> 4, ch = (lane >> 2) & 3;
+        const int64_t p = p0 + u;
+        if ((lane & 3) == 0 && ch < 3 && p < npix) {
+            const int b = (int)(p / HW);
+            const int rem = (int)(p - (int64_t)b * HW);
+            const int yy = rem / W, xx = rem - yy * W;
+            float o = v[0] + bias[ch];
+            if (skip) {
+                const int Hs = H >> 1, Ws = W >> 1;
+                const float* sp = skip + ((int64_t)b * 3 + ch) * Hs * Ws;
+                float acc = 0.f;
+#pragma unroll
+                for (int jy = 0; jy < 4; ++jy) {
+                    const int qy = yy + jy - 2;
+                    if (qy < 0 || (qy & 1) || (qy >> 1) >= Hs) continue;
+#pragma unroll
+                    for (int jx = 0; jx < 4; ++jx) {
+                        const int qx = xx + jx - 2;
+                        if (qx < 0 || (qx & 1) || (qx >> 1) >= Ws) continue;
+                        acc += sp[(qy >> 1) * Ws + (qx >> 1)] * skf[jy * 4 + jx];
+                    }
+                }
+                o += acc;
+            }
+            out[((int64_t)b * 3 + ch) * HW + rem] = o;
         }
     }
 }
@@ -254,14 +331,21 @@ extern "C" int e4s_torgb_f32(const float* x, const float* ws, const float* bias,
         E4S_CHECK_LAUNCH();
         return 0;
     }
-    const int lp = Cin >= 256 ? 64 : (Cin >= 128 ? 32 : (Cin >= 64 ? 16 : 8));
+    if (Cin >= 256) {
+        int64_t blocks = (npix + TW_U * 4 - 1) / (TW_U * 4);
+        if (blocks > 16384) blocks = 16384;
+        hipLaunchKernelGGL(torgb_wide_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, ws, bias, skip, k4, labels, Hm, Wm, R, out, B,
+                           H, W, Cin);
+        E4S_CHECK_LAUNCH();
+        return 0;
+    }
+    const int lp = Cin >= 128 ? 32 : (Cin >= 64 ? 16 : 8);
     const int ppw = 64 / lp;
     int64_t blocks = (npix + (int64_t)ppw * 4 - 1) / ((int64_t)ppw * 4);
     if (blocks > 16384) blocks = 16384;
     dim3 grid((unsigned)blocks), block(256);
 #define E4S_TORGB(LP) hipLaunchKernelGGL(torgb_kernel<LP>, grid, block, 0, st, x, ws, bias, skip, k4, labels, Hm, Wm, R, out, B, H, W, Cin)
-    if (lp == 64) E4S_TORGB(64);
-    else if (lp == 32) E4S_TORGB(32);
+    if (lp == 32) E4S_TORGB(32);
     else if (lp == 16) E4S_TORGB(16);
     else E4S_TORGB(8);
 #undef E4S_TORGB

@@ -796,7 +796,9 @@ def se_gate(pooled, fc1, fc2):
 def region_mean_into(feats, labels, out, num_regions, out_off):
     b, h, w, c = feats.shape
     hm, wm = labels.shape[1:]
-    call("e4s_region_mean_f32", fptr(feats), ptr(labels), hm, wm, fptr(out), b, h, w, c, num_regions,
+    nws = lib.load().e4s_region_mean_ws_floats(b, h * w, c, num_regions)
+    ws = torch.empty(nws, device=feats.device, dtype=torch.float32) if nws else None
+    call("e4s_region_mean_f32", fptr(feats), ptr(labels), hm, wm, fptr(out), fptr(ws), b, h, w, c, num_regions,
          out.shape[2], out_off, stream())
 
 

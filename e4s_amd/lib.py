@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E4S_LIB_PATH") or os.path.join(_HERE, "libe4s_hip.so")      # (E4S_LIB_PATH: A/B runs of two builds)
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -163,7 +163,8 @@ SIGNATURES = {
     "e4s_instnorm_apply_f32": [c_p] * 7 + [c_i] * 5 + [c_p],
     "e4s_se_gate_f32": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
     "e4s_instnorm_finalize_se_f32": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p],
-    "e4s_region_mean_f32": [c_p, c_p, c_i, c_i, c_p] + [c_i] * 7 + [c_p],
+    "e4s_region_mean_f32": [c_p, c_p, c_i, c_i, c_p, c_p] + [c_i] * 7 + [c_p],
+    "e4s_region_mean_ws_floats": [c_i, c_i, c_i, c_i],
     "e4s_conv_wgrad_f32": [ctypes.POINTER(ConvWgradParams), c_p],
     "e4s_conv_wgrad_ws_floats": [ctypes.POINTER(ConvWgradParams)],
     "e4s_conv_wgrad_path": [ctypes.POINTER(ConvWgradParams)],
@@ -216,7 +217,7 @@ SIGNATURES = {
 }
 
 INT64_RETURN = {"e4s_split16_bytes", "e4s_instnorm_ws_doubles", "e4s_conv_bwd_ws_floats", "e4s_grouped_linear_t_ws_floats", "e4s_reduce_parts_ws_floats", "e4s_instnorm_bwd_ws_doubles", "e4s_prelu_bwd_ws_floats", "e4s_conv_wgrad_ws_floats", "e4s_conv_bf16x3_ws_floats", "e4s_conv_region_ws_floats", "e4s_lpips_layer_ws_doubles", "e4s_conv_mfma_ws_floats",
-                "e4s_cosine_ws_doubles", "e4s_colsum_ws_floats", "e4s_scale_dot_ws_floats", "e4s_wino_weights_bytes", "e4s_conv_wino_ws_floats"}       # size queries: return a count, not an error code
+                "e4s_cosine_ws_doubles", "e4s_region_mean_ws_floats", "e4s_colsum_ws_floats", "e4s_scale_dot_ws_floats", "e4s_wino_weights_bytes", "e4s_conv_wino_ws_floats"}       # size queries: return a count, not an error code
 
 _lib = None
 

@@ -568,16 +568,22 @@ int e4s_se_gate_f32(const float* pooled, const float* fc1, const float* fc2, flo
 int e4s_instnorm_finalize_se_f32(const double* ws, float* stats, const float* fc1, const float* fc2, float* gate, int B, int HW,
                                  int C, int Cr, int nslots, float eps, void* stream);
 /* regional average pooling (psp_encoders.py:264-283): out[b, r, out_off + c] = mean over pixels with
- * label r of feats[b, p, c]; exact 0 for empty regions.  feats NHWC [B,H,W,C]. */
-int e4s_region_mean_f32(const float* feats, const uint8_t* labels, int Hm, int Wm, float* out,
+ * label r of feats[b, p, c]; exact 0 for empty regions.  feats NHWC [B,H,W,C], C % 64 == 0, base 16-byte aligned (refused
+ * otherwise); a pixel whose label is >= R belongs to no region.  ws: e4s_region_mean_ws_floats(B, H*W, C, R) floats (per-block
+ * partial sums, added in a fixed order; 0 floats / NULL for maps of <= 256 pixels). */
+int e4s_region_mean_f32(const float* feats, const uint8_t* labels, int Hm, int Wm, float* out, float* ws,
                         int B, int H, int W, int C, int R, int out_stride, int out_off, void* stream);
+int64_t e4s_region_mean_ws_floats(int B, int HW, int C, int R);
 /* Regional style swap (scripts/face_swap.py:117-146, per sample) in one launch: out[b][r] = (sel >> r) & 1 ? src[b][r] : tgt[b][r];
  * region `ear` of a source whose style vector sums to 0 (no ears): the mean of both; region `teeth` likewise empty: the target's;
  * `below` >= 0: the mean of both for that region (belowFace_interpolation).  tgt / src / out [B][R][C], R <= 32. */
 int e4s_swap_styles_f32(const float* tgt, const float* src, float* out, int B, int R, int C, unsigned sel, int ear, int teeth, int below,
                         void* stream);
 /* LocalMLP layer (networks.py:15-39): y[b, r, o] = act(sum_i x[b, r, i]*W[r][o, i]*scale + bias[r][o]) [+ add[o]]
- * W is [R][O][K] (stacked EqualLinear weights); act: 0 none, 1 leaky(alpha). */
+ * W is [R][O][K] (stacked EqualLinear weights); act: 0 none, 1 leaky(alpha).
+ * Two kernels: K <= 1536 with O % 8 == 0 and R * O >= 4096 (the LocalMLP layers) runs several rows per wave with one FMA per
+ * product, every other shape one row per wave.  Which one is a function of (R, O, K) alone, never of B: an output's bits do not
+ * depend on the batch, but the same row of weights may round differently in the last bit under another (R, O). */
 int e4s_grouped_linear_f32(const float* x, const float* W, const float* bias, const float* add, float* y,
                            int B, int R, int K, int O, float scale, int act, float alpha, void* stream);
 
