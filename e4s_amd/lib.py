@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E4S_LIB_PATH") or os.path.join(_HERE, "libe4s_hip.so")      # (E4S_LIB_PATH: A/B runs of two builds)
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -214,6 +214,8 @@ SIGNATURES = {
     "e4s_parser_fc_f32": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p],
     "e4s_gate_add_up2_f32": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p],
     "e4s_parser_head_f32": [c_p] + [c_i] * 8 + [c_p, c_p, c_p, c_p],
+    "e4s_quad_crop_u8": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
+    "e4s_perspective_paste_u8": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
 }
 
 INT64_RETURN = {"e4s_split16_bytes", "e4s_instnorm_ws_doubles", "e4s_conv_bwd_ws_floats", "e4s_grouped_linear_t_ws_floats", "e4s_reduce_parts_ws_floats", "e4s_instnorm_bwd_ws_doubles", "e4s_prelu_bwd_ws_floats", "e4s_conv_wgrad_ws_floats", "e4s_conv_bf16x3_ws_floats", "e4s_conv_region_ws_floats", "e4s_lpips_layer_ws_doubles", "e4s_conv_mfma_ws_floats",

@@ -524,6 +524,21 @@ int e4s_stream_copy_u8(const void* src, void* dst, int64_t bytes, int blocks, vo
 int e4s_paste_u8(const uint8_t* face, const uint8_t* target, const float* mask, uint8_t* out, int B, int H, int W,
                  int Hm, int Wm, void* stream);
 
+/* ---- frame I/O of the swap: aligned crop out of a frame, paste back into it (csrc/align.hip; ABI v17) ----
+ * Pillow's QUAD / PERSPECTIVE transforms with the BILINEAR filter, restated in fp64 in Pillow's operation order (truncated to
+ * uint8).  For output pixel (x, y): xi = x + 0.5, yi = y + 0.5.  Coefficients (8 doubles per image) and windows live in DEVICE
+ * memory; nothing synchronises with the host.
+ * e4s_quad_crop_u8 (src/utils/alignmengt.py:113-140): frames u8 HWC [B,H,W,3] -> out u8 [B,S,S,3], sampled at
+ *   (a0 + a1 xi + a2 yi + a3 xi yi, a4 + a5 xi + a6 yi + a7 xi yi) of the sub-image windows[b] = (x0, y0, x1, y1) (int32 [B,4], what
+ *   img.crop() left; clamped to the frame); 0 outside it.  normalized != NULL: also fp32 NCHW [B,3,S,S] = (v / 255 - 0.5) / 0.5.
+ * e4s_perspective_paste_u8 (scripts/face_swap.py:313-327): out[b,y,x] = bilinear sample of faces u8 [B,S,S,3] at
+ *   ((a0 xi + a1 yi + a2) / d, (a3 xi + a4 yi + a5) / d), d = a6 xi + a7 yi + 1, where that point lies in the face, else
+ *   frames[b,y,x]; frames / out u8 [B,H,W,3]; out may BE frames (then only the covered pixels are touched), no other overlap. */
+int e4s_quad_crop_u8(const uint8_t* frames, const double* coeffs, const int32_t* windows, uint8_t* out, float* normalized, int B,
+                     int H, int W, int S, void* stream);
+int e4s_perspective_paste_u8(const uint8_t* faces, const uint8_t* frames, const double* coeffs, uint8_t* out, int B, int H, int W,
+                             int S, void* stream);
+
 /* ---- layout helpers ------------------------------------------------------------------------ */
 int e4s_nchw_to_nhwc_f32(const float* x, float* y, int B, int C, int H, int W, void* stream);
 int e4s_nhwc_to_nchw_f32(const float* x, float* y, int B, int C, int H, int W, void* stream);
