@@ -1562,3 +1562,95 @@ def parser_head(logits, ncls, size, seg12=False, labels=True, onehot=False, nchw
     nc = torch.empty(b, ncls, hh, ww, device=dev, dtype=torch.float32) if nchw else None
     call("e4s_parser_head_f32", fptr(logits), b, h, w, ncls, cs, hh, ww, 1 if seg12 else 0, ptr(lab), fptr(oh), fptr(nc), stream())
     return lab, oh, nc
+
+
+# ---- Real-ESRNet x4 super-resolution (sr.py) ------------------------------------------------
+def sr_f32():
+    """Whether the dense-block conv runs on the exact fp32 MFMA (PRECISION "f32"); "bf16x3" and "auto" take the split-bf16 path."""
+    return PRECISION == "f32"
+
+
+def rrdb_pack(w, f32):
+    """nn.Conv2d weight [32,Cin,3,3] -> the opaque image e4s_rrdb_conv_f32 reads ([Cin/32][9][32][128 bytes], fp32-typed)."""
+    w = _f32(w)
+    cout, cin, kh, kw = w.shape
+    if cout != 32 or kh != 3 or kw != 3 or cin % 32:
+        raise RuntimeError(f"rrdb_pack: a [32, 32k, 3, 3] weight, got {tuple(w.shape)}")
+    nbytes = lib.load().e4s_rrdb_pack_bytes(cin)
+    out = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
+    call("e4s_rrdb_pack_f32", fptr(w), ptr(out), cin, 0 if f32 else 1, stream())
+    return out
+
+
+def _slice32(t, coff, what):
+    """(pointer, channel stride) of an fp32 NHWC buffer whose 32 channels at coff are read or written in place."""
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 4 or coff < 0 or coff + 32 > t.shape[-1]:
+        raise RuntimeError(f"rrdb_conv({what}): a contiguous fp32 NHWC buffer with 32 channels at offset {coff}")
+    return fptr(t), t.shape[-1]
+
+
+def rrdb_conv(x, cin, w_pack, bias, y, y_coff=0, *, epilogue=0, r0=None, r0_coff=0, s0=1.0, r1=None, r1_coff=0, s1=1.0, up2=False,
+              slope=0.2, f32=None):
+    """Dense-block 3x3 conv: the first cin channels of the NHWC buffer x -> 32 channels at y_coff of the NHWC buffer y (which may
+    be x itself when y_coff >= cin).  epilogue 0: LeakyReLU(slope); 1: acc * s0 + r0; 2: (acc * s0 + r0) * s1 + r1 (r0 / r1: the 32
+    channels at r*_coff of NHWC buffers at the output resolution).  up2: x is read through a nearest x2 upsampling.  Writes y in
+    place and returns it."""
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 4:
+        raise RuntimeError("rrdb_conv: x is a contiguous fp32 NHWC buffer")
+    b, hi, wi, xcs = x.shape
+    ho, wo = (2 * hi, 2 * wi) if up2 else (hi, wi)
+    yp, ycs = _slice32(y, y_coff, "y")
+    if tuple(y.shape[:3]) != (b, ho, wo):
+        raise RuntimeError(f"rrdb_conv: y must hold {(b, ho, wo)} pixels, got {tuple(y.shape[:3])}")
+    p = lib.RrdbParams()
+    p.x, p.w, p.bias, p.y = fptr(x), fptr(w_pack), fptr(_f32(bias)), yp
+    p.B, p.Hi, p.Wi, p.Cin = b, hi, wi, cin
+    p.x_cstride, p.y_cstride, p.y_coff = xcs, ycs, y_coff
+    for name, r, coff in (("r0", r0, r0_coff), ("r1", r1, r1_coff)):
+        if r is not None:
+            rp, rcs = _slice32(r, coff, name)
+            if tuple(r.shape[:3]) != (b, ho, wo):
+                raise RuntimeError(f"rrdb_conv: {name} must hold {(b, ho, wo)} pixels")
+            setattr(p, name, rp)
+            setattr(p, name + "_cstride", rcs)
+            setattr(p, name + "_coff", coff)
+    p.epilogue, p.up2, p.precision = int(epilogue), 1 if up2 else 0, 1 if (sr_f32() if f32 is None else f32) else 0
+    p.s0, p.s1, p.slope = float(s0), float(s1), float(slope)
+    call("e4s_rrdb_conv_f32", ctypes.byref(p), stream())
+    return y
+
+
+def rrdb_head(src, wp, bias, y, y2=None, flip=False):
+    """conv_first: uint8 NHWC [B,H,W,3] (x / 255) or fp32 NCHW [B,3,H,W] -> channels [0, 32) of the NHWC buffers y (and y2)."""
+    if src.dtype == torch.uint8:
+        b, h, w, c = src.shape
+        is_u8 = 1
+    else:
+        src = _f32(src)
+        b, c, h, w = src.shape
+        is_u8 = 0
+    if c != 3:
+        raise RuntimeError(f"rrdb_head: 3-channel images, got shape {tuple(src.shape)}")
+    for t in (y, y2):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape[:3]) != (b, h, w)):
+            raise RuntimeError("rrdb_head: y / y2 are contiguous fp32 NHWC buffers with the image's pixels")
+    call("e4s_rrdb_head_f32", ptr(src.contiguous()), is_u8, 1 if flip else 0, fptr(_f32(wp)), fptr(_f32(bias)), fptr(y), y.shape[-1],
+         fptr(y2), y2.shape[-1] if y2 is not None else 0, b, h, w, stream())
+    return y
+
+
+def rrdb_tail(x, wp, bias, *, u8=False, nchw=True, flip=False):
+    """conv_last on the first 32 channels of NHWC x: the fp32 result (NCHW or NHWC, before any clamp), or with u8 the uint8 HWC
+    image round_half_even(clamp(v, 0, 1) * 255) (channel order reversed with flip)."""
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 4:
+        raise RuntimeError("rrdb_tail: x is a contiguous fp32 NHWC buffer")
+    b, h, w, cs = x.shape
+    if u8:
+        out = torch.empty(b, h, w, 3, device=x.device, dtype=torch.uint8)
+        yf, yu = None, out
+    else:
+        out = torch.empty((b, 3, h, w) if nchw else (b, h, w, 3), device=x.device, dtype=torch.float32)
+        yf, yu = out, None
+    call("e4s_rrdb_tail_f32", fptr(x), cs, fptr(_f32(wp)), fptr(_f32(bias)), fptr(yf), 1 if nchw else 0, ptr(yu), 1 if flip else 0,
+         b, h, w, stream())
+    return out

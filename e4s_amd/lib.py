@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E4S_LIB_PATH") or os.path.join(_HERE, "libe4s_hip.so")      # (E4S_LIB_PATH: A/B runs of two builds)
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -66,6 +66,18 @@ class ConvWgradParams(ctypes.Structure):
         ("Hm", c_i), ("Wm", c_i), ("R", c_i),
         ("B", c_i), ("Hi", c_i), ("Wi", c_i), ("Cin", c_i), ("Ha", c_i), ("Wa", c_i), ("Ho", c_i), ("Wo", c_i), ("Cout", c_i),
         ("istride", c_i), ("ostride", c_i), ("py", c_i), ("px", c_i), ("ntaps", c_i), ("tap_shift", c_i),
+    ]
+
+
+class RrdbParams(ctypes.Structure):
+    """Mirror of ``e4s_rrdb_params`` (include/e4s_hip.h)."""
+    _fields_ = [
+        ("x", c_p), ("w", c_p), ("bias", c_p), ("y", c_p), ("r0", c_p), ("r1", c_p),
+        ("B", c_i), ("Hi", c_i), ("Wi", c_i), ("Cin", c_i),
+        ("x_cstride", c_i), ("y_cstride", c_i), ("y_coff", c_i),
+        ("r0_cstride", c_i), ("r0_coff", c_i), ("r1_cstride", c_i), ("r1_coff", c_i),
+        ("epilogue", c_i), ("up2", c_i), ("precision", c_i),
+        ("s0", c_f), ("s1", c_f), ("slope", c_f),
     ]
 
 
@@ -216,10 +228,15 @@ SIGNATURES = {
     "e4s_parser_head_f32": [c_p] + [c_i] * 8 + [c_p, c_p, c_p, c_p],
     "e4s_quad_crop_u8": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
     "e4s_perspective_paste_u8": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
+    "e4s_rrdb_conv_f32": [ctypes.POINTER(RrdbParams), c_p],
+    "e4s_rrdb_pack_f32": [c_p, c_p, c_i, c_i, c_p],
+    "e4s_rrdb_pack_bytes": [c_i],
+    "e4s_rrdb_head_f32": [c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p],
+    "e4s_rrdb_tail_f32": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p],
 }
 
 INT64_RETURN = {"e4s_split16_bytes", "e4s_instnorm_ws_doubles", "e4s_conv_bwd_ws_floats", "e4s_grouped_linear_t_ws_floats", "e4s_reduce_parts_ws_floats", "e4s_instnorm_bwd_ws_doubles", "e4s_prelu_bwd_ws_floats", "e4s_conv_wgrad_ws_floats", "e4s_conv_bf16x3_ws_floats", "e4s_conv_region_ws_floats", "e4s_lpips_layer_ws_doubles", "e4s_conv_mfma_ws_floats",
-                "e4s_cosine_ws_doubles", "e4s_region_mean_ws_floats", "e4s_colsum_ws_floats", "e4s_scale_dot_ws_floats", "e4s_wino_weights_bytes", "e4s_conv_wino_ws_floats"}       # size queries: return a count, not an error code
+                "e4s_cosine_ws_doubles", "e4s_region_mean_ws_floats", "e4s_colsum_ws_floats", "e4s_scale_dot_ws_floats", "e4s_wino_weights_bytes", "e4s_conv_wino_ws_floats", "e4s_rrdb_pack_bytes"}       # size queries: return a count, not an error code
 
 _lib = None
 

@@ -318,6 +318,26 @@ def synth_module_state_dict(module, seed=0, tag="crit."):
     return out
 
 
+def synth_rrdb_state_dict(net, seed=0):
+    """Seeded weights of an RRDBNet (the reference's or e4s_amd.sr's: chosen by key and shape only): synth_module_state_dict with
+    the dense blocks' conv weights x 0.1 -- the reference's own init scale (rrdbnet_arch.py:29) -- and conv_last scaled so that most
+    pre-clamp outputs lie inside (0, 1): weight / 64, bias + 0.5.  Unscaled, the 69 residual blocks blow the output up to +-50 and
+    the clamp hides almost everything."""
+    sd = synth_module_state_dict(net, seed=seed, tag="rrdb.")
+    for k in sd:
+        if k.startswith("body.") and k.endswith(".weight"):
+            sd[k] = sd[k] * 0.1
+    sd["conv_last.weight"] = sd["conv_last.weight"] / 64
+    sd["conv_last.bias"] = sd["conv_last.bias"] + 0.5
+    return sd
+
+
+def synth_sr_input_u8(batch, h, w, seed=0):
+    """Seeded uint8 NHWC [batch,h,w,3] frame for the super-resolution checks (synth_image cropped to h x w, mapped to 0..255)."""
+    x = synth_image(batch, max(h, w), seed=seed, tag="sr.in")[:, :, :h, :w]
+    return ((x + 1) * 127.5).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
 def synth_image_pair(batch=1, size=1024, seed=0):
     """(y_hat, y): a smooth seeded image in [-1, 1] and a perturbed copy (what a loss network compares during inversion)."""
     import torch.nn.functional as F

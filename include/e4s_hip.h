@@ -680,6 +680,46 @@ int e4s_gate_add_up2_f32(const float* x, const float* gate, const float* add, in
 int e4s_parser_head_f32(const float* logits, int B, int h, int w, int ncls, int cstride, int H, int W, int seg12,
                         uint8_t* labels, float* onehot, float* nchw, void* stream);
 
+/* ---- Real-ESRNet x4 super-resolution (ABI v18; e4s_amd/sr.py, src/pretrained/gpen/sr_model/) -------------------------- */
+/* Dense-block 3x3 conv (stride 1, zero pad 1, 32 outputs, NHWC fp32) with channel strides on both sides: reads the first Cin
+ * channels (a multiple of 32, 32..160) of x [B,Hi,Wi,x_cstride] and writes 32 channels at y_coff of y [B,Ho,Wo,y_cstride]
+ * (Ho, Wo = Hi, Wi; twice that with up2 = 1: the input is read at (y >> 1, x >> 1), nearest x2 folded into the conv).  y may be
+ * the buffer x itself when y_coff >= Cin and up2 = 0 (a dense block's concatenation is never copied); otherwise they must not
+ * overlap.  w: the weights packed by e4s_rrdb_pack_f32 for the same precision.  After + bias[32]:
+ *   epilogue 0  LeakyReLU(slope)
+ *   epilogue 1  acc * s0 + r0               r0 / r1: 32 channels at r*_coff of maps with r*_cstride channels per output pixel
+ *   epilogue 2  (acc * s0 + r0) * s1 + r1   (y may be the slice r1 itself)
+ * precision 0: split-bf16 (three bf16 MFMAs per product, fp32 accumulate); 1: exact fp32 MFMA.  Strides and offsets are
+ * multiples of 4, every base 16-byte aligned.  An output's summation order is fixed: its bits do not depend on the batch. */
+typedef struct {
+    const float* x;
+    const float* w;
+    const float* bias;
+    float* y;
+    const float* r0;
+    const float* r1;
+    int B, Hi, Wi, Cin;
+    int x_cstride, y_cstride, y_coff;
+    int r0_cstride, r0_coff, r1_cstride, r1_coff;
+    int epilogue, up2, precision;
+    float s0, s1, slope;
+} e4s_rrdb_params;
+int e4s_rrdb_conv_f32(const e4s_rrdb_params* p, void* stream);
+/* w [32][Cin][3][3] (nn.Conv2d) -> out [Cin/32][9][32][128 bytes] (e4s_rrdb_pack_bytes(Cin) bytes): 32 floats per row
+ * (split = 0, for precision 1) or [32 hi | 32 lo] bf16 (split = 1, for precision 0) */
+int e4s_rrdb_pack_f32(const float* w, void* out, int Cin, int split, void* stream);
+int64_t e4s_rrdb_pack_bytes(int Cin);
+/* conv_first (3 -> 32, 3x3, pad 1, + bias): src uint8 NHWC [B,H,W,3] (is_u8 = 1, read as x / 255) or fp32 NCHW [B,3,H,W];
+ * flip = 1 reverses the source channel order (BGR <-> RGB).  wp [27][32] ((ky, kx, ci)-major).  Writes channels [0, 32) of y
+ * [B,H,W,y_cstride] and, when given, of y2 [B,H,W,y2_cstride]. */
+int e4s_rrdb_head_f32(const void* src, int is_u8, int flip, const float* wp, const float* bias, float* y, int y_cstride,
+                      float* y2, int y2_cstride, int B, int H, int W, void* stream);
+/* conv_last (32 -> 3, 3x3, pad 1, + bias) of x [B,H,W,x_cstride]; wp [9][3][32].  Outputs (either may be NULL): yf fp32
+ * [B,H,W,3] (nchw = 0) or [B,3,H,W] (nchw = 1), before any clamp; yu uint8 [B,H,W,3] = round-half-to-even(clamp(v, 0, 1) *
+ * 255), channel order reversed with flip = 1 (real_esrnet.py:53-55). */
+int e4s_rrdb_tail_f32(const float* x, int x_cstride, const float* wp, const float* bias, float* yf, int nchw, uint8_t* yu,
+                      int flip, int B, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
