@@ -1654,3 +1654,171 @@ def rrdb_tail(x, wp, bias, *, u8=False, nchw=True, flip=False):
     call("e4s_rrdb_tail_f32", fptr(x), cs, fptr(_f32(wp)), fptr(_f32(bias)), fptr(yf), 1 if nchw else 0, ptr(yu), 1 if flip else 0,
          b, h, w, stream())
     return out
+
+
+# ---- GPEN ParseNet (parsenet.py) ------------------------------------------------------------
+def pconv_out_size(n, stride=1, up2=False):
+    """Output rows of reflect pad 1 + 3x3 at `stride` on n rows (2 n behind a nearest x2 upsampling)."""
+    g = 2 * n if up2 else n
+    if g < 2:
+        raise RuntimeError(f"pconv: reflect padding 1 needs 2 or more rows and columns, got {g}")
+    return (g + 2 - 3) // stride + 1
+
+
+def pconv_pack(w, f32):
+    """nn.Conv2d weight [Cout,Cin,3,3] (both multiples of 32) -> the opaque image e4s_pconv_f32 reads, fp32-typed."""
+    w = _f32(w)
+    cout, cin, kh, kw = w.shape
+    nbytes = lib.load().e4s_pconv_pack_bytes(cin, cout)
+    if kh != 3 or kw != 3 or nbytes == 0:
+        raise RuntimeError(f"pconv_pack: a [32j, 32k, 3, 3] weight, got {tuple(w.shape)}")
+    out = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
+    call("e4s_pconv_pack_f32", fptr(w), ptr(out), cin, cout, 0 if f32 else 1, stream())
+    out.pconv_f32 = bool(f32)                                                # pconv refuses a pack of the other precision
+    return out
+
+
+def _nhwc(t, c, what):
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 4 or t.shape[-1] < c:
+        raise RuntimeError(f"pconv({what}): a contiguous fp32 NHWC buffer of {c} or more channels")
+    return fptr(t), t.shape[-1]
+
+
+def pconv(x, cin, w_pack, cout, y, *, scale=None, bias=None, lrelu=False, r0=None, r1=None, stride=1, up2=False, slope=0.2, f32=None):
+    """Reflect-padded 3x3 conv: the first cin channels of the NHWC buffer x -> the first cout channels of the NHWC buffer y.
+    v = acc * scale + bias, LeakyReLU(slope) with lrelu, then + r0, then + r1 (NHWC buffers at the output resolution).  up2: x is
+    read through a nearest x2 upsampling (stride 1).  Writes y in place and returns it."""
+    xp, xcs = _nhwc(x, cin, "x")
+    b, hi, wi, _ = x.shape
+    if up2 and stride != 1:
+        raise RuntimeError("pconv: up2 goes with stride 1")
+    ho, wo = pconv_out_size(hi, stride, up2), pconv_out_size(wi, stride, up2)
+    p = lib.PconvParams()
+    p.y, p.y_cstride = _nhwc(y, cout, "y")
+    if tuple(y.shape[:3]) != (b, ho, wo):
+        raise RuntimeError(f"pconv: y must hold {(b, ho, wo)} pixels, got {tuple(y.shape[:3])}")
+    f32 = sr_f32() if f32 is None else bool(f32)
+    want = lib.load().e4s_pconv_pack_bytes(cin, cout)
+    if want == 0 or w_pack.dtype != torch.float32 or w_pack.numel() * 4 != want or getattr(w_pack, "pconv_f32", f32) != f32:
+        raise RuntimeError(f"pconv: w_pack is not pconv_pack's image of a [{cout},{cin},3,3] weight in this precision")
+    for name, t in (("w_pack", w_pack), ("y", y), ("scale", scale), ("bias", bias), ("r0", r0), ("r1", r1)):
+        if t is not None and t.device != x.device:
+            raise RuntimeError(f"pconv: {name} is on {t.device}, x on {x.device}")
+    p.x, p.w, p.x_cstride = xp, fptr(w_pack), xcs
+    for name, v in (("scale", scale), ("bias", bias)):
+        if v is not None:
+            if v.numel() != cout:
+                raise RuntimeError(f"pconv: {name} has {v.numel()} entries for {cout} channels")
+            setattr(p, name, fptr(_f32(v)))
+    for name, r in (("r0", r0), ("r1", r1)):
+        if r is not None:
+            rp, rcs = _nhwc(r, cout, name)
+            if tuple(r.shape[:3]) != (b, ho, wo):
+                raise RuntimeError(f"pconv: {name} must hold {(b, ho, wo)} pixels")
+            setattr(p, name, rp)
+            setattr(p, name + "_cstride", rcs)
+    p.B, p.Hi, p.Wi, p.Cin, p.Cout = b, hi, wi, cin, cout
+    p.stride, p.up2, p.lrelu, p.precision = int(stride), 1 if up2 else 0, 1 if lrelu else 0, 1 if f32 else 0
+    p.slope = float(slope)
+    call("e4s_pconv_f32", ctypes.byref(p), stream())
+    return y
+
+
+def parsenet_head(src, wp, bias, y, flip=False):
+    """The first conv: uint8 NHWC [B,H,W,3] (x / 255 * 2 - 1) or fp32 NCHW [B,3,H,W] -> the NHWC buffer y [B,H,W,Cout]."""
+    if src.dtype == torch.uint8:
+        b, h, w, c = src.shape
+        is_u8 = 1
+    else:
+        src = _f32(src)
+        b, c, h, w = src.shape
+        is_u8 = 0
+    if c != 3:
+        raise RuntimeError(f"parsenet_head: 3-channel images, got shape {tuple(src.shape)}")
+    cout = wp.shape[-1]
+    if y.dtype != torch.float32 or not y.is_contiguous() or tuple(y.shape) != (b, h, w, cout) or tuple(wp.shape) != (27, cout):
+        raise RuntimeError("parsenet_head: y is a contiguous fp32 NHWC buffer [B,H,W,Cout], wp [27,Cout]")
+    call("e4s_parsenet_head_f32", ptr(src.contiguous()), is_u8, 1 if flip else 0, fptr(_f32(wp)), fptr(_f32(bias)), fptr(y), cout,
+         b, h, w, stream())
+    return y
+
+
+def parsenet_tail(x, cin, wp, bias, *, mask=True, labels=False, logits=False):
+    """out_mask_conv on the first cin channels of NHWC x, wp [9,cin,20] -> (mask uint8 [B,H,W] of 0 / 255, labels uint8 [B,H,W],
+    logits fp32 [B,19,H,W]); what is not asked for is None."""
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 4 or tuple(wp.shape) != (9, cin, 20) or bias.numel() != 19:
+        raise RuntimeError("parsenet_tail: x is a contiguous fp32 NHWC buffer, wp [9,Cin,20], bias [19]")
+    b, h, w, cs = x.shape
+    dev = x.device
+    m = torch.empty(b, h, w, device=dev, dtype=torch.uint8) if mask else None
+    lab = torch.empty(b, h, w, device=dev, dtype=torch.uint8) if labels else None
+    lg = torch.empty(b, 19, h, w, device=dev, dtype=torch.float32) if logits else None
+    call("e4s_parsenet_tail_f32", fptr(x), cs, cin, fptr(_f32(wp)), fptr(_f32(bias)), ptr(m), ptr(lab), fptr(lg), b, h, w, stream())
+    return m, lab, lg
+
+
+# ---- pasting restored faces into a frame (face_paste.py) --------------------------------------
+def warp_affine(src, inv, out_hw):
+    """OpenCV's warpAffine (bilinear, constant border 0) of a uint8 [H,W,3] or fp32 [H,W] image; inv: the six doubles of the inverse
+    map (a00, a01, b0, a10, a11, b1), destination -> source."""
+    hd, wd = int(out_hw[0]), int(out_hw[1])
+    if src.dtype == torch.uint8 and src.dim() == 3 and src.shape[2] == 3:
+        dst, is_f32 = torch.empty(hd, wd, 3, device=src.device, dtype=torch.uint8), 0
+    elif src.dtype == torch.float32 and src.dim() == 2:
+        dst, is_f32 = torch.empty(hd, wd, device=src.device, dtype=torch.float32), 1
+    else:
+        raise RuntimeError(f"warp_affine: a uint8 [H,W,3] or fp32 [H,W] image, got {tuple(src.shape)} {src.dtype}")
+    a = [float(v) for v in inv]
+    if len(a) != 6:
+        raise RuntimeError("warp_affine: six coefficients")
+    call("e4s_warp_affine", ptr(src.contiguous()), ptr(dst), is_f32, src.shape[0], src.shape[1], hd, wd, *a, stream())
+    return dst
+
+
+def mask_prep(mask_u8, thres):
+    """uint8 [B,H,W] -> fp32 mask / 255 with a frame of thres pixels zeroed."""
+    if mask_u8.dtype != torch.uint8 or mask_u8.dim() != 3:
+        raise RuntimeError("mask_prep: uint8 [B,H,W] masks")
+    b, h, w = mask_u8.shape
+    out = torch.empty(b, h, w, device=mask_u8.device, dtype=torch.float32)
+    call("e4s_mask_prep_f32", ptr(mask_u8.contiguous()), fptr(out), b, h, w, int(thres), stream())
+    return out
+
+
+def blur_pass(x, taps, axis, out=None):
+    """One pass of a separable filter over fp32 [B,H,W] along x (axis 1) or y (axis 0), BORDER_REFLECT_101."""
+    x = _f32(x)
+    if x.dim() != 3 or taps.dim() != 1 or taps.device != x.device:
+        raise RuntimeError("blur_pass: fp32 [B,H,W] maps and a 1-D tap tensor on the same device")
+    out = torch.empty_like(x) if out is None else out
+    b, h, w = x.shape
+    call("e4s_blur_pass_f32", fptr(x), fptr(out), fptr(_f32(taps)), taps.numel(), b, h, w, int(axis), stream())
+    return out
+
+
+def binomial3_u8(x):
+    """cv2.filter2D with [1 2 1] x [1 2 1] / 16 on uint8 [B,H,W,C]."""
+    if x.dtype != torch.uint8 or x.dim() != 4:
+        raise RuntimeError("binomial3_u8: uint8 [B,H,W,C] images")
+    x = x.contiguous()
+    out = torch.empty_like(x)
+    b, h, w, c = x.shape
+    call("e4s_binomial3_u8", ptr(x), ptr(out), b, h, w, c, stream())
+    return out
+
+
+def merge_blend(masks, faces, bg, out=None):
+    """masks fp32 [n,H,W], faces uint8 [n,H,W,3] (both warped into the frame), bg uint8 [H,W,3] -> the blended frame (out may be bg)."""
+    if bg.dtype != torch.uint8 or bg.dim() != 3 or bg.shape[2] != 3 or not bg.is_contiguous():
+        raise RuntimeError("merge_blend: bg is a contiguous uint8 [H,W,3] frame")
+    h, w, _ = bg.shape
+    n = 0 if masks is None else masks.shape[0]
+    if n and (tuple(masks.shape) != (n, h, w) or tuple(faces.shape) != (n, h, w, 3) or masks.dtype != torch.float32
+              or faces.dtype != torch.uint8 or masks.device != bg.device or faces.device != bg.device):
+        raise RuntimeError("merge_blend: masks fp32 [n,H,W] and faces uint8 [n,H,W,3] at the frame's size and on its device")
+    out = torch.empty_like(bg) if out is None else out
+    if tuple(out.shape) != tuple(bg.shape) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != bg.device:
+        raise RuntimeError("merge_blend: out is a contiguous uint8 frame like bg")
+    call("e4s_merge_blend_u8", fptr(masks.contiguous()) if n else None, ptr(faces.contiguous()) if n else None, ptr(bg), ptr(out), n, h, w,
+         stream())
+    return out

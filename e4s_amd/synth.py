@@ -347,3 +347,17 @@ def synth_image_pair(batch=1, size=1024, seed=0):
     up = lambda t: F.interpolate(t, size=(size, size), mode="bilinear", align_corners=False)
     y = (0.6 * up(base) + 0.2 * up(mid)).clamp_(-1, 1)
     return (y + 0.15 * up(pert)).clamp_(-1, 1), y
+
+
+def synth_parsenet_state_dict(net, seed=0):
+    """Seeded weights of a GPEN ParseNet (the reference's or e4s_amd.parsenet's: chosen by key and shape only):
+    synth_module_state_dict -- BatchNorm scale 1 +- 0.1 with running statistics near (0, 1), so folding them is not a no-op -- with
+    every block's conv2 weight x 0.5 (up to 18 residual blocks in a row stay within an order or two of the input) and
+    out_mask_conv's bias x 10: the class biases then spread about as far as the conv's own output, so that both groups of
+    MASK_COLORMAP (classes 0 / 14 / 18 and the rest) occur in a mask, in areas rather than as noise."""
+    sd = synth_module_state_dict(net, seed=seed, tag="parsenet.")
+    for k in sd:
+        if k.endswith(".conv2.conv2d.weight"):
+            sd[k] = sd[k] * 0.5
+    sd["out_mask_conv.conv2d.bias"] = sd["out_mask_conv.conv2d.bias"] * 10.0
+    return sd

@@ -720,6 +720,69 @@ int e4s_rrdb_head_f32(const void* src, int is_u8, int flip, const float* wp, con
 int e4s_rrdb_tail_f32(const float* x, int x_cstride, const float* wp, const float* bias, float* yf, int nchw, uint8_t* yu,
                       int flip, int B, int H, int W, void* stream);
 
+/* ---- GPEN ParseNet (ABI v19; e4s_amd/parsenet.py, src/pretrained/gpen/face_parse/) -------------------------------------- */
+/* ReflectionPad2d(1) + 3x3 conv, NHWC fp32, Cin and Cout multiples of 32: x [B,Hi,Wi,x_cstride] (the first Cin channels) -> y
+ * [B,Ho,Wo,y_cstride] (the first Cout channels; channels past Cout are not touched).  The reflect map (index -1 reads 1, index
+ * n reads n - 2) applies on the grid the conv runs on: Hi x Wi, or with up2 = 1 its nearest x2 upsampling, whose position g reads
+ * source g >> 1 (stride 1 only); neither a padded nor an upsampled map is written.  stride 1 or 2: Ho = (G + 2 - 3) / stride + 1
+ * on a grid of G >= 2 rows.  w: the weights packed by e4s_pconv_pack_f32 for the same precision.  Epilogue, in this order:
+ *   v = acc * scale[c] + bias[c]     (scale, bias [Cout] or NULL: 1 and 0; eval-mode BatchNorm folded on the host)
+ *   v = LeakyReLU(v, slope)          when lrelu = 1
+ *   v = r0 + v, then v = r1 + v      r0 / r1 NULL or NHWC maps [B,Ho,Wo,r*_cstride] (the first Cout channels); y may be r0 or r1
+ * precision 0: split-bf16 (three bf16 MFMAs per product, fp32 accumulate); 1: exact fp32 MFMA.  Channel strides are multiples of
+ * 4, every base 16-byte aligned, y must not overlap x.  An output's summation order is fixed: its bits do not depend on the
+ * batch or on where its tile lies. */
+typedef struct {
+    const float* x;
+    const float* w;
+    const float* scale;
+    const float* bias;
+    const float* r0;
+    const float* r1;
+    float* y;
+    int B, Hi, Wi, Cin, Cout;
+    int x_cstride, y_cstride, r0_cstride, r1_cstride;
+    int stride, up2, lrelu, precision;
+    float slope;
+} e4s_pconv_params;
+int e4s_pconv_f32(const e4s_pconv_params* p, void* stream);
+/* w [Cout][Cin][3][3] (nn.Conv2d) -> out [Cout/32][Cin/32][9][32][128 bytes] (e4s_pconv_pack_bytes(Cin, Cout) bytes; 0 for
+ * sizes the kernel does not take): 32 floats per row (split = 0, for precision 1) or [32 hi | 32 lo] bf16 (split = 1) */
+int e4s_pconv_pack_f32(const float* w, void* out, int Cin, int Cout, int split, void* stream);
+int64_t e4s_pconv_pack_bytes(int Cin, int Cout);
+/* The encoder's first conv (3 -> Cout, Cout % 8 == 0, Cout <= 64; reflect pad 1, + bias): src uint8 NHWC [B,H,W,3] (is_u8 = 1,
+ * read as x / 255 * 2 - 1 evaluated in double and rounded to float, face_parsing.py:59-63) or fp32 NCHW [B,3,H,W] taken as it
+ * is; flip = 1 reverses the source channel order (BGR <-> RGB).  wp [27][Cout] ((ky, kx, ci)-major).  y NHWC [B,H,W,Cout]. */
+int e4s_parsenet_head_f32(const void* src, int is_u8, int flip, const float* wp, const float* bias, float* y, int Cout, int B,
+                          int H, int W, void* stream);
+/* out_mask_conv (Cin -> 19, Cin % 4 == 0, Cin <= 64; reflect pad 1, + bias[19]) of x [B,H,W,x_cstride]; wp [9][Cin][20]
+ * (tap, input channel, class; the 20th column is padding and must be finite).  Outputs (each may be NULL, not all): labels uint8 [B,H,W] the
+ * first maximum over the classes (torch.argmax); mask uint8 [B,H,W] = MASK_COLORMAP[label] of face_parsing.py:30 (classes 0,
+ * 14, 18 -> 0, every other -> 255); logits fp32 [B,19,H,W]. */
+int e4s_parsenet_tail_f32(const float* x, int x_cstride, int Cin, const float* wp, const float* bias, uint8_t* mask,
+                          uint8_t* labels, float* logits, int B, int H, int W, void* stream);
+
+/* ---- pasting GPEN's restored faces into a frame (ABI v19; e4s_amd/face_paste.py, face_enhancement.py:44-49,68-108) -------- */
+/* cv2.warpAffine(src, M, (Wd, Hd), flags=3) with the constant border 0, restated from OpenCV's imgwarp.cpp: src / dst uint8
+ * [H,W,3] (is_f32 = 0) or fp32 [H,W] (is_f32 = 1), must not overlap, sizes <= 32767.  a00 .. b1: the INVERSE map (destination
+ * -> source) in double, inverted by the caller as OpenCV does.  Coordinates go through OpenCV's fixed-point grid (1/1024 per
+ * row / column term, 1/32 pixel fractions, cvRound = half to even); uint8 uses its integer weights and (sum + 16384) >> 15,
+ * fp32 its float weights summed tap 0 to 3; taps outside the source read 0. */
+int e4s_warp_affine(const void* src, void* dst, int is_f32, int Hs, int Ws, int Hd, int Wd, double a00, double a01, double b0,
+                    double a10, double a11, double b1, void* stream);
+/* out[b,y,x] = mask[b,y,x] / 255 as fp32, 0 inside a frame of thres pixels (face_enhancement.py:45-46); [B,H,W] */
+int e4s_mask_prep_f32(const uint8_t* mask, float* out, int B, int H, int W, int thres, void* stream);
+/* One pass of a separable filter over fp32 [B,H,W]: K taps (odd, <= 1023; device memory) along x (axis = 1) or y (axis = 0),
+ * BORDER_REFLECT_101, fp32 accumulation in tap order.  in and out must differ. */
+int e4s_blur_pass_f32(const float* in, float* out, const float* taps, int K, int B, int H, int W, int axis, void* stream);
+/* cv2.filter2D(x, -1, [1 2 1] x [1 2 1] / 16) on uint8 [B,H,W,C], BORDER_REFLECT_101, rounded half to even; in != out */
+int e4s_binomial3_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, int C, void* stream);
+/* face_enhancement.py:100-108 for one frame: masks fp32 [n,H,W] and faces uint8 [n,H,W,3] already warped into the frame; per
+ * pixel the faces in order, face f takes the pixel where masks[f] - running mask > 0; out = convertScaleAbs(bg * (1 - m) +
+ * face * m) in fp32 (|.|, round half to even, saturate).  bg, out uint8 [H,W,3]; out may be bg.  n = 0 copies bg. */
+int e4s_merge_blend_u8(const float* masks, const uint8_t* faces, const uint8_t* bg, uint8_t* out, int nfaces, int H, int W,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
