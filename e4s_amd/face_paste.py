@@ -1,6 +1,7 @@
 """Restored faces back into the frame, on the device: FaceEnhancement.process(aligned=False), face_enhancement.py:68-110.
 
-Once a detector has produced boxes and five landmarks per face, the frame stays on the device until the blended frame is done:
+Once a detector has produced boxes and five landmarks per face, the frame stays on the device until the blended frame is done.  The
+detector is e4s_amd.retinaface.RetinaFaceDetection (FaceRestorer(detector=...) calls it when process gets no boxes):
 
     reference (per face)                                             here
     ---------------------------------------------------------------  ---------------------------------------------------------
@@ -18,8 +19,8 @@ cv2 is not a dependency.  warp_affine, the Gaussian blur and the 3x3 filter rest
 fixed-point coordinate grid and weights, getGaussianKernel's formula, BORDER_REFLECT_101); they are cross-checked against
 scipy.ndimage and fp64 restatements in the tests, not against cv2 itself.  Two deliberate differences from the reference's call:
 the mask is blurred in fp32 (the reference hands GaussianBlur a float64 array), and the landmark arithmetic is float64 (the
-reference rounds the points to float32 first).  Detection (RetinaFace), the resize of the frame to the SR size, align types other
-than similarity and in_size != out_size stay outside."""
+reference rounds the points to float32 first).  The resize of the frame to the SR size, align types other than similarity and
+in_size != out_size stay outside."""
 import numpy as np
 import torch
 
@@ -171,28 +172,39 @@ def gpen_restore(generator):
 class FaceRestorer(object):
     """face_enhancement.py:68-110 with the detector's output as an argument.  restore: a callable on device uint8 BGR batches
     [n,S,S,3] -> the same (gpen_restore(e4s_amd.gpen.FullGenerator(..)) is the reference's FaceGAN); parser: an
-    e4s_amd.parsenet.FaceParse (anything with .masks(faces_u8, bgr=True))."""
+    e4s_amd.parsenet.FaceParse (anything with .masks(faces_u8, bgr=True)); detector: an e4s_amd.retinaface.RetinaFaceDetection
+    (anything with .detect_device(frame_u8)), asked when process is given neither boxes nor landmarks."""
 
-    def __init__(self, restore, parser, in_size=512, out_size=None, threshold=0.9):
+    def __init__(self, restore, parser, in_size=512, out_size=None, threshold=0.9, detector=None):
         out_size = in_size if out_size is None else out_size
         if in_size != out_size:
             raise NotImplementedError("FaceRestorer: in_size != out_size (the reference's cv2.resize of the face) is not provided")
         if not callable(restore):
             raise TypeError("FaceRestorer: restore is a callable on uint8 face batches (see gpen_restore)")
-        self.restore, self.parser = restore, parser
+        self.restore, self.parser, self.detector = restore, parser, detector
         self.in_size, self.threshold = in_size, threshold
         self.reference_5pts = reference_5pts(in_size)
 
     @torch.no_grad()
-    def process(self, frame_u8, boxes, landms, background=None):
+    def process(self, frame_u8, boxes=None, landms=None, background=None):
         """frame_u8: device uint8 [H,W,3] (BGR); boxes [n,5] (x0, y0, x1, y1, score) and landms [n,10] (five x, then five y) on
-        the host, as RetinaFace returns them; background: the frame the faces are blended over (the SR frame), same size; default
+        the host, as RetinaFace returns them -- both None: the detector given at construction finds them on the device (one
+        device-to-host copy of its at most 750 x 15 floats); background: the frame the faces are blended over (the SR frame), same size; default
         the frame itself.  Returns (blended frame, aligned faces [n',S,S,3], restored faces [n',S,S,3]) on the device."""
         if not frame_u8.is_cuda:
             raise RuntimeError("FaceRestorer runs on the ROCm device only (no CPU path)")
         if frame_u8.dtype != torch.uint8 or frame_u8.dim() != 3 or frame_u8.shape[2] != 3:
             raise ValueError("FaceRestorer.process: a uint8 [H,W,3] frame")
         frame_u8 = frame_u8.contiguous()
+        if (boxes is None) != (landms is None):
+            raise ValueError("FaceRestorer.process: boxes and landms come together (or neither, with a detector)")
+        if boxes is None:
+            if self.detector is None:
+                raise ValueError("FaceRestorer.process: no boxes / landms and no detector (FaceRestorer(detector=RetinaFaceDetection(..)))")
+            dets, lms, counts = self.detector.detect_device(frame_u8)
+            n = int(counts[0])
+            both = torch.cat((dets[0, :n], lms[0, :n]), 1).cpu().numpy()
+            boxes, landms = both[:, :5], both[:, 5:]
         bg = frame_u8 if background is None else background.contiguous()
         if tuple(bg.shape) != tuple(frame_u8.shape) or bg.dtype != torch.uint8:
             raise ValueError("FaceRestorer.process: background is a uint8 frame of the frame's size (resize the frame to the SR size first)")

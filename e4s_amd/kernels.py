@@ -1757,6 +1757,144 @@ def parsenet_tail(x, cin, wp, bias, *, mask=True, labels=False, logits=False):
     return m, lab, lg
 
 
+# ---- RetinaFace-R50 face detector (retinaface.py) ------------------------------------------
+def rconv_out_size(n, k, stride=1):
+    """Output rows of a zero-padded (k / 2) k x k conv at `stride` on n rows: ceil(n / stride) for k = 1 and 3."""
+    return (n + 2 * (k // 2) - k) // stride + 1
+
+
+def rconv_pack(w, f32):
+    """nn.Conv2d weight [Cout,Cin,k,k] (Cin % 32 == 0, Cout % 64 == 0, k 1 or 3) -> the opaque image e4s_rconv_f32 reads."""
+    w = _f32(w)
+    cout, cin, kh, kw = w.shape
+    nbytes = lib.load().e4s_rconv_pack_bytes(cin, cout, kh) if kh == kw else 0
+    if nbytes == 0:
+        raise RuntimeError(f"rconv_pack: a [64j, 32k, 1|3, 1|3] weight, got {tuple(w.shape)}")
+    out = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
+    call("e4s_rconv_pack_f32", fptr(w), ptr(out), cin, cout, kh, 0 if f32 else 1, stream())
+    out.rconv_f32 = bool(f32)                                                # rconv refuses a pack of the other precision
+    out.rconv_shape = (cout, cin, kh)
+    return out
+
+
+def rconv(x, cin, w_pack, cout, k, y, *, y_coff=0, bias=None, act=False, slope=0.0, r0=None, r0_after=False, stride=1, f32=None):
+    """Zero-padded k x k conv (k 1 or 3): the first cin channels of the NHWC buffer x -> channels y_coff .. y_coff + cout of the NHWC
+    buffer y.  v = acc + bias; + r0 (r0_after False); LeakyReLU(slope) with act (slope 0: ReLU); + r0 (r0_after True).  r0: an NHWC
+    map at the output resolution, or a smaller one that is read through a nearest upsampling to it.  Writes y in place."""
+    xp, xcs = _nhwc(x, cin, "x")
+    b, hi, wi, _ = x.shape
+    ho, wo = rconv_out_size(hi, k, stride), rconv_out_size(wi, k, stride)
+    p = lib.RconvParams()
+    p.y, p.y_cstride = _nhwc(y, y_coff + cout, "y")
+    if tuple(y.shape[:3]) != (b, ho, wo):
+        raise RuntimeError(f"rconv: y must hold {(b, ho, wo)} pixels, got {tuple(y.shape[:3])}")
+    f32 = sr_f32() if f32 is None else bool(f32)
+    if getattr(w_pack, "rconv_shape", None) != (cout, cin, k) or getattr(w_pack, "rconv_f32", None) != f32:
+        raise RuntimeError(f"rconv: w_pack is not rconv_pack's image of a [{cout},{cin},{k},{k}] weight in this precision")
+    for name, t in (("w_pack", w_pack), ("y", y), ("bias", bias), ("r0", r0)):
+        if t is not None and t.device != x.device:
+            raise RuntimeError(f"rconv: {name} is on {t.device}, x on {x.device}")
+    p.x, p.w, p.x_cstride, p.y_coff = xp, fptr(w_pack), xcs, int(y_coff)
+    if bias is not None:
+        if bias.numel() != cout:
+            raise RuntimeError(f"rconv: bias has {bias.numel()} entries for {cout} channels")
+        p.bias = fptr(_f32(bias))
+    if r0 is not None:
+        p.r0, p.r0_cstride = _nhwc(r0, cout, "r0")
+        if r0.shape[0] != b:
+            raise RuntimeError("rconv: r0 has another batch size")
+        if tuple(r0.shape[1:3]) != (ho, wo):
+            p.r0_H, p.r0_W = r0.shape[1], r0.shape[2]
+        p.r0_mode = 2 if r0_after else 1
+    p.B, p.Hi, p.Wi, p.Cin, p.Cout = b, hi, wi, cin, cout
+    p.k, p.stride, p.act, p.precision, p.slope = int(k), int(stride), 1 if act else 0, 1 if f32 else 0, float(slope)
+    call("e4s_rconv_f32", ctypes.byref(p), stream())
+    return y
+
+
+def retina_prep(frames_u8, out, scale=1.0):
+    """uint8 BGR [B,H,W,3] -> out fp32 [B,Hd,Wd,3] minus (104, 117, 123); Hd x Wd other than H x W: a half-pixel bilinear resize
+    first, source coordinate (d + 0.5) * scale - 0.5."""
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3 or not frames_u8.is_contiguous():
+        raise RuntimeError("retina_prep: contiguous uint8 frames [B,H,W,3]")
+    b, h, w, _ = frames_u8.shape
+    if out.dtype != torch.float32 or out.dim() != 4 or out.shape[0] != b or out.shape[-1] != 3 or not out.is_contiguous():
+        raise RuntimeError("retina_prep: out is a contiguous fp32 buffer [B,Hd,Wd,3]")
+    call("e4s_retina_prep_f32", ptr(frames_u8), fptr(out), b, h, w, out.shape[1], out.shape[2], float(scale), stream())
+    return out
+
+
+def retina_stem(x, wp, bias, y):
+    """The 7x7 stride-2 stem (BatchNorm folded, ReLU) on e4s_conv_smallcin_f32, into the caller's buffer y."""
+    b, hi, wi, cin = x.shape
+    _, ho, wo, cout = y.shape
+    if (ho, wo) != ((hi + 6 - 7) // 2 + 1, (wi + 6 - 7) // 2 + 1) or y.shape[0] != b or not y.is_contiguous():
+        raise RuntimeError("retina_stem: y holds the stride-2 output of x")
+    call("e4s_conv_smallcin_f32", fptr(_f32(x)), fptr(_f32(wp)), fptr(_f32(bias)), fptr(y), b, hi, wi, cin, ho, wo, cout, 7, 2, 3, 1, stream())
+    return y
+
+
+def retina_pool(x, y):
+    """nn.MaxPool2d(3, 2, padding=1) of NHWC x into the caller's buffer y (e4s_maxpool3s2p1_f32)."""
+    b, hi, wi, c = x.shape
+    if tuple(y.shape) != (b, (hi - 1) // 2 + 1, (wi - 1) // 2 + 1, c) or not y.is_contiguous():
+        raise RuntimeError("retina_pool: y holds the stride-2 output of x")
+    call("e4s_maxpool3s2p1_f32", fptr(_f32(x)), fptr(y), b, hi, wi, c, stream())
+    return y
+
+
+def retina_geom(im_h, im_w, resize=1.0, steps=(8, 16, 32), min_sizes=((16, 32), (64, 128), (256, 512))):
+    """The prior grid of an im_h x im_w network input (prior_box.py:14): lib.RetinaGeom."""
+    g = lib.RetinaGeom()
+    g.imH, g.imW, g.nlevel, g.resize = int(im_h), int(im_w), len(steps), float(resize)
+    base = 0
+    for l, st in enumerate(steps):
+        g.lh[l], g.lw[l], g.step[l], g.base[l] = -(-im_h // st), -(-im_w // st), st, base
+        g.min_size[l][0], g.min_size[l][1] = float(min_sizes[l][0]), float(min_sizes[l][1])
+        base += g.lh[l] * g.lw[l] * 2
+    g.N = base
+    return g
+
+
+def retina_head(x, wp, bias, geom, level, boxes, scores, landms, raw=None):
+    """One level's fused heads + softmax + prior + decode: x NHWC [B,lh,lw,>=256] -> that level's rows of boxes [B,N,4], scores
+    [B,N], landms [B,N,10] (and of raw = (loc, conf, landms) when given)."""
+    xp, xcs = _nhwc(x, 256, "x")
+    b = x.shape[0]
+    if tuple(x.shape[1:3]) != (geom.lh[level], geom.lw[level]) or tuple(wp.shape) != (256, 32) or bias.numel() != 32:
+        raise RuntimeError("retina_head: x is the level's map, wp [256,32], bias [32]")
+    for t, shp in ((boxes, (b, geom.N, 4)), (scores, (b, geom.N)), (landms, (b, geom.N, 10))):
+        if tuple(t.shape) != shp or not t.is_contiguous():
+            raise RuntimeError(f"retina_head: an output is not a contiguous {shp} buffer")
+    rl, rc, rm = raw if raw is not None else (None, None, None)
+    if raw is not None and (tuple(rl.shape) != (b, geom.N, 4) or tuple(rc.shape) != (b, geom.N, 2) or tuple(rm.shape) != (b, geom.N, 10)):
+        raise RuntimeError("retina_head: raw = (loc [B,N,4], conf [B,N,2], landms [B,N,10])")
+    call("e4s_retina_head_f32", xp, xcs, fptr(_f32(wp)), fptr(_f32(bias)), ctypes.byref(geom), int(level), b, fptr(boxes), fptr(scores),
+         fptr(landms), fptr(rl), fptr(rc), fptr(rm), stream())
+
+
+def retina_decode(loc, conf, lm, geom, boxes, scores, landms):
+    """prior + decode + scaling of the network's raw outputs loc [B,N,4], conf [B,N,2] (softmaxed), lm [B,N,10]."""
+    b = loc.shape[0]
+    for t, shp in ((loc, (b, geom.N, 4)), (conf, (b, geom.N, 2)), (lm, (b, geom.N, 10)), (boxes, (b, geom.N, 4)), (scores, (b, geom.N)),
+                   (landms, (b, geom.N, 10))):
+        if tuple(t.shape) != shp:
+            raise RuntimeError(f"retina_decode: expected a {shp} tensor, got {tuple(t.shape)}")
+    call("e4s_retina_decode_f32", fptr(_f32(loc)), fptr(_f32(conf)), fptr(_f32(lm)), ctypes.byref(geom), b, fptr(boxes), fptr(scores),
+         fptr(landms), stream())
+
+
+def retina_select(boxes, landms, sorted_scores, sorted_idx, conf_thr, nms_thr, top_k, keep_top_k, ss, dets, lm_out, counts):
+    """Threshold, top_k, greedy NMS, keep_top_k and the landmark re-layout on score-sorted candidates: -> dets [B,K,5], lm_out
+    [B,K,10], counts int32 [B]."""
+    b, n, _ = boxes.shape
+    if sorted_idx.dtype != torch.int64 or counts.dtype != torch.int32 or tuple(dets.shape) != (b, keep_top_k, 5) \
+            or tuple(lm_out.shape) != (b, keep_top_k, 10) or tuple(sorted_scores.shape) != (b, n) or tuple(sorted_idx.shape) != (b, n):
+        raise RuntimeError("retina_select: sorted_idx int64 [B,N], counts int32 [B], dets [B,K,5], lm_out [B,K,10]")
+    call("e4s_retina_select_f32", fptr(boxes), fptr(landms), fptr(sorted_scores), ptr(sorted_idx), b, n, float(conf_thr), float(nms_thr),
+         int(top_k), int(keep_top_k), float(ss), fptr(dets), fptr(lm_out), ptr(counts), stream())
+
+
 # ---- pasting restored faces into a frame (face_paste.py) --------------------------------------
 def warp_affine(src, inv, out_hw):
     """OpenCV's warpAffine (bilinear, constant border 0) of a uint8 [H,W,3] or fp32 [H,W] image; inv: the six doubles of the inverse

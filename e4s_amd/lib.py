@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E4S_LIB_PATH") or os.path.join(_HERE, "libe4s_hip.so")      # (E4S_LIB_PATH: A/B runs of two builds)
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -89,6 +89,28 @@ class PconvParams(ctypes.Structure):
         ("x_cstride", c_i), ("y_cstride", c_i), ("r0_cstride", c_i), ("r1_cstride", c_i),
         ("stride", c_i), ("up2", c_i), ("lrelu", c_i), ("precision", c_i),
         ("slope", c_f),
+    ]
+
+
+class RconvParams(ctypes.Structure):
+    """Mirror of ``e4s_rconv_params`` (include/e4s_hip.h)."""
+    _fields_ = [
+        ("x", c_p), ("w", c_p), ("bias", c_p), ("r0", c_p), ("y", c_p),
+        ("B", c_i), ("Hi", c_i), ("Wi", c_i), ("Cin", c_i), ("Cout", c_i),
+        ("x_cstride", c_i), ("y_cstride", c_i), ("y_coff", c_i), ("r0_cstride", c_i),
+        ("r0_H", c_i), ("r0_W", c_i),
+        ("k", c_i), ("stride", c_i), ("act", c_i), ("r0_mode", c_i), ("precision", c_i),
+        ("slope", c_f),
+    ]
+
+
+class RetinaGeom(ctypes.Structure):
+    """Mirror of ``e4s_retina_geom`` (include/e4s_hip.h)."""
+    _fields_ = [
+        ("imH", c_i), ("imW", c_i), ("nlevel", c_i), ("N", c_i),
+        ("lh", c_i * 3), ("lw", c_i * 3), ("step", c_i * 3), ("base", c_i * 3),
+        ("min_size", (c_f * 2) * 3),
+        ("resize", c_f),
     ]
 
 
@@ -254,10 +276,17 @@ SIGNATURES = {
     "e4s_blur_pass_f32": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
     "e4s_binomial3_u8": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
     "e4s_merge_blend_u8": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
+    "e4s_rconv_f32": [ctypes.POINTER(RconvParams), c_p],
+    "e4s_rconv_pack_f32": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
+    "e4s_rconv_pack_bytes": [c_i, c_i, c_i],
+    "e4s_retina_prep_f32": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_d, c_p],
+    "e4s_retina_head_f32": [c_p, c_i, c_p, c_p, ctypes.POINTER(RetinaGeom), c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    "e4s_retina_decode_f32": [c_p, c_p, c_p, ctypes.POINTER(RetinaGeom), c_i, c_p, c_p, c_p, c_p],
+    "e4s_retina_select_f32": [c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_f, c_i, c_i, c_f, c_p, c_p, c_p, c_p],
 }
 
 INT64_RETURN = {"e4s_split16_bytes", "e4s_instnorm_ws_doubles", "e4s_conv_bwd_ws_floats", "e4s_grouped_linear_t_ws_floats", "e4s_reduce_parts_ws_floats", "e4s_instnorm_bwd_ws_doubles", "e4s_prelu_bwd_ws_floats", "e4s_conv_wgrad_ws_floats", "e4s_conv_bf16x3_ws_floats", "e4s_conv_region_ws_floats", "e4s_lpips_layer_ws_doubles", "e4s_conv_mfma_ws_floats",
-                "e4s_cosine_ws_doubles", "e4s_region_mean_ws_floats", "e4s_colsum_ws_floats", "e4s_scale_dot_ws_floats", "e4s_wino_weights_bytes", "e4s_conv_wino_ws_floats", "e4s_rrdb_pack_bytes", "e4s_pconv_pack_bytes"}       # size queries: return a count, not an error code
+                "e4s_cosine_ws_doubles", "e4s_region_mean_ws_floats", "e4s_colsum_ws_floats", "e4s_scale_dot_ws_floats", "e4s_wino_weights_bytes", "e4s_conv_wino_ws_floats", "e4s_rrdb_pack_bytes", "e4s_pconv_pack_bytes", "e4s_rconv_pack_bytes"}       # size queries: return a count, not an error code
 
 _lib = None
 

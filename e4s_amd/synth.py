@@ -361,3 +361,29 @@ def synth_parsenet_state_dict(net, seed=0):
             sd[k] = sd[k] * 0.5
     sd["out_mask_conv.conv2d.bias"] = sd["out_mask_conv.conv2d.bias"] * 10.0
     return sd
+
+
+def synth_retinaface_state_dict(net, seed=0):
+    """Seeded weights of a RetinaFace(cfg_re50) (the reference's or e4s_amd.retinaface's: chosen by key and shape only):
+    synth_module_state_dict -- BatchNorm scale 1 +- 0.1 with running statistics near (0, 1), so folding them is not a no-op -- and,
+    so that activations neither die nor blow up through the 50 layers: the stem conv / 64 (its input is mean-subtracted pixels of
+    +-128), every conv in front of a ReLU x sqrt(2), and each bottleneck's bn3 scale x 0.5 (a block then adds about a quarter of
+    its input's variance to the identity).  The class heads' weights x 4 spread the two-class softmax over (0, 1), so that some
+    priors pass the 0.9 threshold."""
+    sd = synth_module_state_dict(net, seed=seed, tag="retinaface.")
+    for k in sd:
+        if sd[k].dim() == 4 and k != "body.conv1.weight" and not k.endswith("conv3.weight") and ".downsample." not in k \
+                and "Head" not in k and not k.endswith(("conv3X3.0.weight", "conv5X5_2.0.weight", "conv7x7_3.0.weight")):
+            sd[k] = sd[k] * math.sqrt(2.0)
+        if k.startswith("body.") and k.endswith(".bn3.weight"):
+            sd[k] = sd[k] * 0.5
+        if k.startswith("ClassHead.") and k.endswith(".weight"):
+            sd[k] = sd[k] * 4.0
+    sd["body.conv1.weight"] = sd["body.conv1.weight"] * (math.sqrt(2.0) / 64.0)
+    return sd
+
+
+def synth_retinaface_frame_u8(batch, h, w, seed=0):
+    """Seeded uint8 BGR frames [batch,h,w,3] for the detector checks (synth_image cropped to h x w, mapped to 0..255)."""
+    x = synth_image(batch, max(h, w), seed=seed, tag="retinaface.in")[:, :, :h, :w]
+    return ((x + 1) * 127.5).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()

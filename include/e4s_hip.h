@@ -783,6 +783,69 @@ int e4s_binomial3_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, int C
 int e4s_merge_blend_u8(const float* masks, const uint8_t* faces, const uint8_t* bg, uint8_t* out, int nfaces, int H, int W,
                        void* stream);
 
+/* ---- RetinaFace-R50 face detector (ABI v20; e4s_amd/retinaface.py, src/pretrained/gpen/face_detect/) ---------------------- */
+/* Zero-padded conv, k = 1 or 3 (padding k / 2), stride 1 or 2, NHWC fp32, Cin a multiple of 32, Cout of 64, any Hi and Wi: x
+ * [B,Hi,Wi,x_cstride] (the first Cin channels) -> channels y_coff .. y_coff + Cout - 1 of y [B,Ho,Wo,y_cstride] (every other
+ * channel of y is left alone), Ho = (Hi + 2 (k / 2) - k) / stride + 1.  w: the weights packed by e4s_rconv_pack_f32 for the same
+ * precision.  Epilogue, in this order:
+ *   v = acc + bias[c]                      bias [Cout] or NULL (eval-mode BatchNorm folded on the host)
+ *   v = v + r0                             when r0_mode = 1
+ *   v = v > 0 ? v : v * slope              when act = 1 (slope 0: ReLU)
+ *   v = v + r0                             when r0_mode = 2
+ * r0 (NULL exactly when r0_mode = 0): an NHWC map [B,Ho,Wo,r0_cstride] (r0_H = r0_W = 0), or [B,r0_H,r0_W,r0_cstride] read
+ * through a nearest upsampling to Ho x Wo (source index min(floorf(dst * ((float)in / (float)out)), in - 1), as ATen's
+ * interpolate(mode="nearest") computes it); its first Cout channels are read.  y must not overlap x.  precision 0: split-bf16
+ * (three bf16 MFMAs per product, fp32 accumulate), 1: exact fp32 MFMA.  The summation order of an output is (tap, 32-channel
+ * chunk, k-step), whatever the batch or the position. */
+typedef struct {
+    const float* x;
+    const float* w;
+    const float* bias;
+    const float* r0;
+    float* y;
+    int B, Hi, Wi, Cin, Cout;
+    int x_cstride, y_cstride, y_coff, r0_cstride;
+    int r0_H, r0_W;
+    int k, stride, act, r0_mode, precision;
+    float slope;
+} e4s_rconv_params;
+int e4s_rconv_f32(const e4s_rconv_params* p, void* stream);
+/* w [Cout][Cin][k][k] (nn.Conv2d) -> out [Cout/64][k*k][Cin/32][64][128 bytes] (e4s_rconv_pack_bytes bytes; 0 for sizes the
+ * kernel does not take): 32 floats per row (split = 0, for precision 1) or [32 hi | 32 lo] bf16 (split = 1) */
+int e4s_rconv_pack_f32(const float* w, void* out, int Cin, int Cout, int k, int split, void* stream);
+int64_t e4s_rconv_pack_bytes(int Cin, int Cout, int k);
+/* src uint8 BGR [B,H,W,3] -> dst fp32 [B,Hd,Wd,3] minus (104, 117, 123) (retinaface_detection.py:73).  Hd x Wd other than H x W:
+ * a bilinear resize with half-pixel centres first, source coordinate (d + 0.5) * scale - 0.5 in double, clamped to the image
+ * (the shrink of retinaface_detection.py:67-70 with scale = 1 / ss). */
+int e4s_retina_prep_f32(const uint8_t* src, float* dst, int B, int H, int W, int Hd, int Wd, double scale, void* stream);
+/* The prior grid of one image size: level l has lh[l] x lw[l] cells of `step[l]` pixels with two anchors of min_size[l][0..1]
+ * each; base[l] = index of its first prior (levels, rows, columns, anchors in this order; N priors in all). */
+typedef struct {
+    int imH, imW, nlevel, N;
+    int lh[3], lw[3], step[3], base[3];
+    float min_size[3][2];
+    float resize;
+} e4s_retina_geom;
+/* One pyramid level's Bbox / Class / Landmark heads in one pass: x [B,lh,lw,x_cstride] (256 channels) times wp [256][32] + bias
+ * [32], column anchor * 16 + t (t 0..3 loc, 4..5 conf, 6..15 landmarks); then the 2-class softmax, the cell's prior
+ * (prior_box.py:21-28, computed in double and rounded to float), decode / decode_landm (box_utils.py, variances 0.1 / 0.2) and
+ * * (W, H, ..) / resize.  Writes rows base[level] .. of boxes [B,N,4], scores [B,N] and landms [B,N,10] (x, y interleaved), and
+ * of the network's raw outputs raw_loc [B,N,4], raw_conf [B,N,2] (after the softmax), raw_lm [B,N,10] (all three or none). */
+int e4s_retina_head_f32(const float* x, int x_cstride, const float* wp, const float* bias, const e4s_retina_geom* g, int level,
+                        int B, float* boxes, float* scores, float* landms, float* raw_loc, float* raw_conf, float* raw_lm,
+                        void* stream);
+/* The same prior + decode + scaling from the network's raw outputs (every level at once) */
+int e4s_retina_decode_f32(const float* loc, const float* conf, const float* lm, const e4s_retina_geom* g, int B, float* boxes,
+                          float* scores, float* landms, void* stream);
+/* retinaface_detection.py:97-131 per image, on the device: sorted_scores / sorted_idx [B,N] = the scores sorted descending
+ * (stable, so equal scores keep the lower prior index first) and their prior indices (int64).  Candidates: score > conf_thr,
+ * the first top_k of them; greedy NMS as py_cpu_nms.py:18-36 (+ 1 areas; a box is dropped unless ovr <= nms_thr); the first
+ * keep_top_k survivors -> dets [B,keep_top_k,5] (x1, y1, x2, y2, score) / ss and lm_out [B,keep_top_k,10] (five x, then five
+ * y) / ss, rows past counts[b] zero.  keep_top_k * 4 + min(top_k, N) bytes of LDS must stay within 60 KB. */
+int e4s_retina_select_f32(const float* boxes, const float* landms, const float* sorted_scores, const int64_t* sorted_idx, int B,
+                          int N, float conf_thr, float nms_thr, int top_k, int keep_top_k, float ss, float* dets, float* lm_out,
+                          int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
