@@ -956,6 +956,40 @@ def adam_multi_dev(ps, grads, ms, vs, steps, lr, beta1, beta2, eps, weight_decay
          _ptr_array(steps, torch.int64), float(lr), ptr(lr_dev), float(beta1), float(beta2), float(eps), float(weight_decay), stream())
 
 
+def ranger_ws_floats(sizes, row_lens):
+    """Floats of row-sum workspace ranger_multi_dev needs for tensors of `sizes` elements whose centralised rows are `row_lens` long
+    (0: the tensor's gradient is not centralised)."""
+    n = len(sizes)
+    if n != len(row_lens):
+        raise RuntimeError("ranger_ws_floats: list lengths differ")
+    need = lib.load().e4s_ranger_multi_ws_floats(n, (ctypes.c_int64 * n)(*sizes), (ctypes.c_int64 * n)(*row_lens))
+    if need < 0:
+        raise RuntimeError("ranger_ws_floats: a row length must be 0 or divide its tensor's size")
+    return int(need)
+
+
+def ranger_multi_dev(ps, grads, ms, vs, slows, row_lens, steps, ws, lr, beta1, beta2, eps, weight_decay, alpha, k, nsma_threshold,
+                     lr_dev=None):
+    """One Ranger step (src/training/ranger.py:78-164) of lists of tensors: 2 * ceil(len / 40) launches, capturable.  steps: device
+    int64[1] tensors, already advanced; row_lens: length of a centralised row per tensor or 0; ws: fp32 workspace of at least
+    ranger_ws_floats(...) floats (may be None when nothing is centralised).  The gradients are only read."""
+    n = len(ps)
+    if not (n == len(grads) == len(ms) == len(vs) == len(slows) == len(row_lens) == len(steps)):
+        raise RuntimeError("ranger_multi_dev: list lengths differ")
+    if lr_dev is not None and (lr_dev.dtype != torch.float64 or not lr_dev.is_cuda):
+        raise RuntimeError("ranger_multi_dev: lr_dev must be a device float64 tensor")
+    if ws is not None and (ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous()):
+        raise RuntimeError("ranger_multi_dev: ws must be a contiguous device float32 tensor")
+    for p, g in zip(ps, grads):
+        if g.shape != p.shape:
+            raise RuntimeError("ranger_multi_dev: gradient shape differs from its parameter's")
+    sizes = (ctypes.c_int64 * n)(*[p.numel() for p in ps])
+    rows = (ctypes.c_int64 * n)(*[int(r) for r in row_lens])
+    call("e4s_ranger_multi_dev_f32", n, _ptr_array(ps), _ptr_array(grads), _ptr_array(ms), _ptr_array(vs), _ptr_array(slows), sizes, rows,
+         _ptr_array(steps, torch.int64), ptr(ws), 0 if ws is None else ws.numel(), float(lr), ptr(lr_dev), float(beta1), float(beta2),
+         float(eps), float(weight_decay), float(alpha), int(k), float(nsma_threshold), stream())
+
+
 def ema_multi_(dsts, srcs, decay):
     """dst <- dst * decay + src * (1 - decay) for lists of tensors: ceil(len / 48) launches; version counters advance."""
     n = len(dsts)

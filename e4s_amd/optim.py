@@ -9,6 +9,7 @@ hyper-parameters and state as torch.optim.Adam (no amsgrad).
   one launch per group; the learning rate lives in a device float64 (`sync_hyper()` uploads `group["lr"]` when it changed: coach.py:377-381's
   schedule reaches a captured graph); the updates of ALL parameters go out as multi-tensor launches (e4s_adam_multi_dev_f32, 48 tensors
   per launch with their pointers in the kernel arguments): Net3's 344 tensors are 1 + 8 launches per step, not 688.
+* `Ranger`: the reference's second optimiser (src/training/ranger.py; coach.py:241-243) on the same plumbing, always capturable.
 Measured at 1024^2: 11.6 ms replayed vs 11.9 ms eager on the l2-only step, 20.4 vs ~25 ms with the LPIPS and identity terms."""
 import os
 
@@ -158,6 +159,165 @@ class FusedAdam(torch.optim.Optimizer):
                 # the kernel wrote through the raw pointer: advance the version counter like an in-place torch op would, or
                 # every weight pack keyed on (data_ptr, _version) (e4s_amd/packs.py) would keep serving the OLD weights
                 torch.autograd.graph.increment_version(p)
+        return loss
+
+
+class Ranger(FusedAdam):
+    """The reference's Ranger (src/training/ranger.py: RAdam + Lookahead + gradient centralisation; coach.py:241-243 builds it for every
+    `--optim_name` but 'adam') as a fused, capturable step: the reference's constructor signature, `param_groups` defaults (the unused
+    `step_counter` included) and state keys (`step`, `exp_avg`, `exp_avg_sq`, `slow_buffer`), restated exactly, quirks included:
+
+    * `use_gc` is stored and never consulted (ranger.py:117 tests only the gradient's rank): `use_gc=False` centralises as well.  A
+      gradient of more than `gc_gradient_threshold` dimensions (1, or 3 with `gc_conv_only=True`) has the mean of every row -- index 0
+      of the tensor, numel / shape[0] elements -- subtracted before the moments see it.
+    * `alpha` and `N_sma_threshhold` (the reference's spelling) are read from the optimiser's attributes, `k`, `lr`, `betas`, `eps` and
+      `weight_decay` from the group.
+    * a parameter without a gradient is skipped and its step count stays; `slow_buffer` is a copy of the parameter taken when its state
+      is created, before the first update.  The 10-entry `radam_buffer` of the reference is only a cache and is not reproduced.
+
+    One code path, always capturable: the step counts of a group live in one flat device int64 tensor (`state[p]["step"]` is a view of
+    it; host ints and separate tensors of a loaded state are re-packed), the learning rate in a device float64, and the rectification
+    branch and the `step % k` Lookahead test are decided in the kernel from the device step count (csrc/ranger.hip), so a replayed
+    `GraphedStep` takes the right branch on every step.  All parameters of a group go out as 1 + 2 * ceil(n / 40) launches: the step
+    advance, then per 40 tensors the row sums of the centralised gradients (ordered partial sums in a per-group workspace, allocated
+    outside any capture) and the fused update.  The centralised gradient is never written: `p.grad` is left as it was (the reference
+    centralises its own `.float()` view of it, which no caller reads afterwards).  fp32 parameters with dense fp32 gradients only; there
+    is no CPU path."""
+
+    def __init__(self, params, lr=1e-3, alpha=0.5, k=6, N_sma_threshhold=5, betas=(.95, 0.999), eps=1e-5, weight_decay=0,
+                 use_gc=True, gc_conv_only=False):
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f'Invalid slow update rate: {alpha}')
+        if not 1 <= k:
+            raise ValueError(f'Invalid lookahead steps: {k}')
+        if not lr > 0:
+            raise ValueError(f'Invalid Learning Rate: {lr}')
+        if not eps > 0:
+            raise ValueError(f'Invalid eps: {eps}')
+        defaults = dict(lr=lr, alpha=alpha, k=k, step_counter=0, betas=betas, N_sma_threshhold=N_sma_threshhold, eps=eps,
+                        weight_decay=weight_decay)
+        torch.optim.Optimizer.__init__(self, params, defaults)
+        self.N_sma_threshhold = N_sma_threshhold
+        self.alpha = alpha
+        self.k = k
+        self.use_gc = use_gc
+        self.gc_gradient_threshold = 3 if gc_conv_only else 1
+        self.capturable = True
+        self._dev = {}                    # FusedAdam's per-group record + {"ws": fp32 row-sum workspace | None, "ws_key": live parameters}
+
+    # ---- host helpers (pure Python, double) -------------------------------------------------------------------------------------------
+    @staticmethod
+    def radam_coefficients(step, beta1, beta2, threshold):
+        """(N_sma, step_size, adaptive) of ranger.py:133-142 for step count `step` >= 1, as Python evaluates them (double); the kernel
+        evaluates the same expressions from the device step count."""
+        import math
+        beta2_t = beta2 ** step
+        N_sma_max = 2 / (1 - beta2) - 1
+        N_sma = N_sma_max - 2 * step * beta2_t / (1 - beta2_t)
+        if N_sma > threshold:
+            step_size = math.sqrt((1 - beta2_t) * (N_sma - 4) / (N_sma_max - 4) * (N_sma - 2) / N_sma * N_sma_max / (N_sma_max - 2)) / (
+                1 - beta1 ** step)
+            return N_sma, step_size, True
+        return N_sma, 1.0 / (1 - beta1 ** step), False
+
+    @staticmethod
+    def gc_rows(shape, gc_conv_only=False):
+        """(rows, row_len) of the centralisation of a gradient of `shape` (ranger.py:117-118: the mean over every dimension but the
+        first), or None when it is not centralised: at most 1 dimension (3 with gc_conv_only), or no elements."""
+        shape = tuple(int(s) for s in shape)
+        n = 1
+        for s in shape:
+            n *= s
+        if len(shape) <= (3 if gc_conv_only else 1) or n == 0:
+            return None
+        return shape[0], n // shape[0]
+
+    # ---- GraphedStep protocol (sync_hyper / load_state_dict / written_tensors / _flat_steps: FusedAdam's) -------------------------------
+    def hyper_by_value(self):
+        """What a captured step bakes into its kernel arguments besides addresses: per group (betas, eps, weight_decay, k), then alpha, the
+        rectification threshold and the centralisation threshold (it decides which tensors have row sums)."""
+        return tuple((tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), int(g["k"])) for g in self.param_groups) + (
+            float(self.alpha), float(self.N_sma_threshhold), int(self.gc_gradient_threshold))
+
+    def captured_state_ptrs(self):
+        """Addresses a captured step has baked into its kernel arguments: per group the flat step tensor and the row-sum workspace, per
+        parameter exp_avg / exp_avg_sq / slow_buffer."""
+        out = []
+        for gi, group in enumerate(self.param_groups):
+            d = self._dev.get(gi)
+            out.append(d["flat"].data_ptr() if d is not None and d.get("flat") is not None else 0)
+            out.append(d["ws"].data_ptr() if d is not None and d.get("ws") is not None else 0)
+            for p in group["params"]:
+                st = self.state.get(p)
+                if st and "exp_avg" in st:
+                    out.extend((st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["slow_buffer"].data_ptr()))
+        return tuple(out)
+
+    def _check(self, p):
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise RuntimeError("Ranger handles contiguous fp32 parameters")
+        if p.grad.is_sparse:
+            raise RuntimeError("Ranger optimizer does not support sparse gradients")
+        if p.grad.device != p.device or p.grad.dtype != torch.float32:
+            raise RuntimeError("Ranger needs a dense fp32 gradient on the parameter's device")
+
+    def _workspace(self, d, live, row_lens, device, capturing):
+        """The group's row-sum workspace for the live parameters: allocated on the first step and whenever their set changes, never
+        inside a capture (the memory would belong to the graph's pool and the captured launches could not be told from stale ones)."""
+        key = tuple(id(p) for p in live)
+        if d.get("ws_key") != key:
+            if capturing:
+                raise RuntimeError("Ranger: the set of parameters with a gradient changed inside a graph capture; take one eager step "
+                                   "with the same set first")
+            need = K.ranger_ws_floats([p.numel() for p in live], row_lens)
+            d["ws"] = torch.empty(need, device=device, dtype=torch.float32) if need else None
+            d["ws_key"] = key
+        return d["ws"]
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        capturing = torch.cuda.is_current_stream_capturing()
+        if not capturing:
+            self.sync_hyper()
+        for gi, group in enumerate(self.param_groups):
+            b1, b2 = group["betas"]
+            live = [p for p in group["params"] if p.grad is not None]
+            if not live:
+                continue
+            for p in live:
+                self._check(p)
+                st = self.state[p]
+                if "exp_avg" not in st:
+                    if capturing:
+                        raise RuntimeError("Ranger: a parameter got its first gradient inside a graph capture; take one eager step first")
+                    st["step"] = 0
+                    st["exp_avg"] = torch.zeros_like(p)
+                    st["exp_avg_sq"] = torch.zeros_like(p)
+                    st["slow_buffer"] = p.detach().clone(memory_format=torch.contiguous_format)
+            dev = live[0].device
+            d = self._group_dev(gi, group, dev)
+            d["hyper"] = self.hyper_by_value()
+            with_state = [p for p in group["params"] if p in self.state and "exp_avg" in self.state[p]]
+            flat = self._flat_steps(d, with_state, dev)
+            if len(live) == len(with_state):
+                K.advance_steps(flat)                            # one launch for the whole group
+            else:                                                # some parameters have no gradient this step: theirs do not advance
+                for p in live:
+                    K.advance_steps(self.state[p]["step"])
+            rows = [self.gc_rows(p.shape) if p.dim() > self.gc_gradient_threshold else None for p in live]
+            row_lens = [r[1] if r else 0 for r in rows]
+            ws = self._workspace(d, live, row_lens, dev, capturing)
+            grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in live]
+            K.ranger_multi_dev(live, grads, [self.state[p]["exp_avg"] for p in live], [self.state[p]["exp_avg_sq"] for p in live],
+                               [self.state[p]["slow_buffer"] for p in live], row_lens, [self.state[p]["step"] for p in live], ws,
+                               group["lr"], b1, b2, group["eps"], group["weight_decay"], self.alpha, group["k"], self.N_sma_threshhold,
+                               lr_dev=d["lr"])
+            # the kernels wrote through raw pointers: keep the weight packs keyed on (data_ptr, _version) (e4s_amd/packs.py) honest
+            torch.autograd.graph.increment_version(live)
         return loss
 
 

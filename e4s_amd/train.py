@@ -46,6 +46,25 @@ def accumulate(model1, model2, decay=0.999):
         K.ema_multi_(dst, src, decay)
 
 
+def configure_optimizers(net, disc, optim_name="adam", learning_rate=1e-4, train_D=True, d_reg_every=-1):
+    """Coach.configure_optimizers (src/training/coach.py:232-244; the defaults are those of train_options.py) on the native
+    optimisers: (optimizer, optimizer_D) over the parameters that require a gradient.  'adam' gives FusedAdam(capturable=True) where
+    the reference builds torch.optim.Adam, any other name Ranger, as coach.py:241-243 does; D's learning rate is scaled by
+    d_reg_every / (d_reg_every + 1) when the lazy R1 regularisation is on; optimizer_D is None without train_D.  Both kinds can be
+    captured by TrainIteration.graphed_{g,d,r1}_step."""
+    from .optim import FusedAdam, Ranger
+    params = [p for p in net.parameters() if p.requires_grad]
+    params_d = [p for p in disc.parameters() if p.requires_grad] if train_D else None
+    d_reg_ratio = d_reg_every / (d_reg_every + 1) if d_reg_every > 0 else 1
+    if optim_name == "adam":
+        optimizer = FusedAdam(params, lr=learning_rate, capturable=True)
+        optimizer_d = FusedAdam(params_d, lr=learning_rate * d_reg_ratio, capturable=True) if train_D else None
+    else:
+        optimizer = Ranger(params, lr=learning_rate)
+        optimizer_d = Ranger(params_d, lr=learning_rate * d_reg_ratio) if train_D else None
+    return optimizer, optimizer_d
+
+
 class _MseFn(torch.autograd.Function):
     """F.mse_loss (mean reduction) with the sum on the native ordered column sum: bit-reproducible, and free of the hipMemsetAsync that
     ATen's global reduce issues for its semaphores (a memset NODE in a captured step; kernels.sum_all says why that matters here)."""

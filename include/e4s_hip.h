@@ -440,6 +440,27 @@ int e4s_adam_multi_dev_f32(int count, float* const* p, const float* const* grad,
                            const int64_t* const* step, double lr, const double* lr_dev, double beta1, double beta2, double eps,
                            double weight_decay, void* stream);
 int e4s_ema_multi_f32(int count, float* const* dst, const float* const* src, const int64_t* n, double decay, void* stream);
+/* Ranger = RAdam + Lookahead + gradient centralisation (src/training/ranger.py:78-164) as a multi-tensor capturable step (ABI v21;
+ * csrc/ranger.hip, e4s_amd/optim.py:Ranger).  Arrays as in e4s_adam_multi_dev_f32 (HOST arrays of device pointers, handed to the kernels
+ * by value, 40 tensors per launch) plus slow[i] (Lookahead's slow weights) and row_len[i]: the length of one row (index 0) of tensor i if
+ * its gradient is centralised -- it must divide n[i] -- or 0 if it is not.  step[i]: DEVICE int64, already advanced (e4s_advance_i64), >= 1
+ * (a count < 1 leaves its tensor untouched); lr_dev as above.  Per tensor, in fp32 with the coefficients evaluated in double in the
+ * kernel from the device step count t:
+ *   g' = g - mean(row of g)             (never written: grad[] is only read)
+ *   v = v b2 + (1 - b2) g' g';  m = m b1 + (1 - b1) g'
+ *   N_max = 2 / (1 - b2) - 1;  N = N_max - 2 t b2^t / (1 - b2^t)
+ *   N > nsma_threshold:  s = sqrt((1 - b2^t) (N - 4) / (N_max - 4) (N - 2) / N  N_max / (N_max - 2)) / (1 - b1^t);  else s = 1 / (1 - b1^t)
+ *   p += -(wd lr) p  (wd != 0);  p += -(s lr) m / (sqrt(v) + eps)  resp.  p += -(s lr) m
+ *   t % k == 0:  slow += alpha (p - slow);  p = slow          (slow is neither read nor written on the other steps)
+ * Two launches per 40 tensors, the same on every step: the row sums of the centralised tensors into ws (ordered partial sums, no
+ * floating-point atomics: bit-reproducible, and a tensor's result does not depend on the other tensors of the call), then the fused
+ * update.  ws: ws_floats >= e4s_ranger_multi_ws_floats(count, n, row_len) floats owned by the caller (the query returns -1 for a row_len
+ * that is negative or does not divide n).  No allocation, copy or synchronisation: capturable. */
+int64_t e4s_ranger_multi_ws_floats(int count, const int64_t* n, const int64_t* row_len);
+int e4s_ranger_multi_dev_f32(int count, float* const* p, const float* const* grad, float* const* m, float* const* v, float* const* slow,
+                             const int64_t* n, const int64_t* row_len, const int64_t* const* step, float* ws, int64_t ws_floats,
+                             double lr, const double* lr_dev, double beta1, double beta2, double eps, double weight_decay, double alpha,
+                             int k, double nsma_threshold, void* stream);
 /* 3x3 stride-1 conv as Winograd F(2,3) along the image rows on the split-bf16 matrix-core path (csrc/conv_wino.hip): 1.5x fewer MFMAs than
  * e4s_conv_bf16x3_f32 for the encoder's Conv2d(3x3, stride 1) layers (src/models/encoders/helpers.py:128-137).
  * e4s_wino_weights_f32: w9 [9][Cout][Cin] (tap-packed, e4s_pack_taps_f32) -> the kernel's transformed, hi/lo-split operand
