@@ -180,6 +180,8 @@ __global__ void strided_place_kernel(const float* __restrict__ in, float* __rest
 }
 
 // ---- regional average pooling backward: dfeat[b,p,c] (+)= dcodes[b, r(p), off + c] / count[b, r(p)] -------------------
+// A pixel whose label is >= R belongs to no region, as in the forward (`if (lab[u] >= 0 && lab[u] < R)` in region_mean_kernel,
+// encoder.hip): it is not counted, its dfeat is 0 (left as it is when accumulating), and neither `sc` nor `cnt` is indexed with it.
 __global__ void region_count_kernel(const uint8_t* __restrict__ labels, int Hm, int Wm, int* __restrict__ cnt, int H,
                                     int W, int R) {
     __shared__ int sc[16];
@@ -188,7 +190,8 @@ __global__ void region_count_kernel(const uint8_t* __restrict__ labels, int Hm, 
     __syncthreads();
     for (int p = threadIdx.x; p < H * W; p += blockDim.x) {
         const int yy = p / W, xx = p - yy * W;
-        atomicAdd(&sc[labels[((int64_t)b * Hm + nearest_src(yy, Hm, H)) * Wm + nearest_src(xx, Wm, W)]], 1);   // integer
+        const int lab = labels[((int64_t)b * Hm + nearest_src(yy, Hm, H)) * Wm + nearest_src(xx, Wm, W)];
+        if (lab < R) atomicAdd(&sc[lab], 1);                            // integer; R <= 16 (checked by the entry point)
     }
     __syncthreads();
     if ((int)threadIdx.x < R) cnt[b * R + threadIdx.x] = sc[threadIdx.x];
@@ -206,8 +209,13 @@ __global__ void region_mean_bwd_kernel(const float* __restrict__ dcodes, const u
     const int yy = (int)(r % H);
     const int64_t b = r / H;
     const int lab = labels[(b * Hm + nearest_src(yy, Hm, H)) * Wm + nearest_src(xx, Wm, W)];
-    const float inv = 1.f / (float)cnt[b * R + lab];                    // the pixel itself is in the region: count >= 1
-    f32x4 v = *reinterpret_cast<const f32x4*>(dcodes + (b * R + lab) * stride + off + c) * inv;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (lab < R) {
+        const float inv = 1.f / (float)cnt[b * R + lab];                // the pixel itself is in the region: count >= 1
+        v = *reinterpret_cast<const f32x4*>(dcodes + (b * R + lab) * stride + off + c) * inv;
+    } else if (accumulate) {
+        return;                                                         // no region: dfeat keeps its bits
+    }
     if (accumulate) v += *reinterpret_cast<const f32x4*>(dfeat + i * 4);
     *reinterpret_cast<f32x4*>(dfeat + i * 4) = v;
 }

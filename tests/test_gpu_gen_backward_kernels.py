@@ -10,50 +10,12 @@ import pytest
 import torch
 
 import gen_bwd_cases as gc
+from guarded_alloc import PAD, SENTINEL, _GuardedTorch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-SENTINEL = 12345.0
-PAD = 64                    # floats on either side of a guarded tensor (keeps the 16-byte alignment of the vector kernels)
 U = 2.0 ** -24
 _WORST = {}                 # kernel output -> largest observed error / bound on random data
-
-
-class _GuardedTorch:
-    """Stands in for `torch` inside e4s_amd.kernels: every tensor a wrapper allocates (outputs and workspaces) is the middle of a
-    SENTINEL-filled buffer and starts as NaN, so a write next to it and an element left unwritten both show."""
-
-    def __init__(self):
-        self.bufs = []
-
-    def __getattr__(self, name):
-        return getattr(torch, name)
-
-    def empty(self, *shape, device=None, dtype=torch.float32):
-        shape = tuple(shape[0]) if len(shape) == 1 and isinstance(shape[0], (tuple, list, torch.Size)) else tuple(int(v) for v in shape)
-        assert dtype == torch.float32
-        n = 1
-        for v in shape:
-            n *= v
-        buf = torch.full((n + 2 * PAD,), SENTINEL, device=device, dtype=dtype)
-        buf[PAD:PAD + n] = float("nan")
-        self.bufs.append((buf, n))
-        return buf[PAD:PAD + n].view(shape)
-
-    def empty_like(self, t):
-        return self.empty(*t.shape, device=t.device, dtype=t.dtype)
-
-    def place(self, t):
-        """a copy of `t` on the device inside a guarded buffer (for tensors a kernel updates in place)"""
-        out = self.empty(*t.shape, device=DEV)
-        out.copy_(t)
-        return out
-
-    def check(self):
-        torch.cuda.synchronize()
-        for buf, n in self.bufs:
-            assert bool((buf[:PAD] == SENTINEL).all()) and bool((buf[PAD + n:] == SENTINEL).all()), "a neighbour of an output was written"
-        self.bufs.clear()
 
 
 @pytest.fixture
