@@ -33,7 +33,8 @@ def _digest():
     h = hashlib.sha256()
     h.update(" ".join(_extra_flags()).encode())
     h.update(repr(sorted(PER_FILE_FLAGS.items())).encode())
-    files = sources() + [os.path.join(CSRC, "common.h"), os.path.join(ROOT, "include", "e4s_hip.h")]
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
+    files = sources() + headers + [os.path.join(ROOT, "include", "e4s_hip.h")]
     for f in files:
         h.update(f.encode())
         with open(f, "rb") as fh:
@@ -41,46 +42,8 @@ def _digest():
     return h.hexdigest()
 
 
-def build(force=False, verbose=False):
-    """Compile every HIP source for gfx950 and link libe4s_hip.so in-tree.  Returns the path.
-    E4S_BUILD_OUT=<path.so>: a SECOND library beside the product one (profiling builds with E4S_BUILD_ABLATIONS=1, A/B builds; loaded
-    with E4S_LIB_PATH): own object directory, no stamp, the product library is not touched."""
-    alt = os.environ.get("E4S_BUILD_OUT")
-    if alt:
-        return _build_to(os.path.abspath(alt), os.path.join(os.path.dirname(os.path.abspath(alt)), "obj_" + os.path.basename(alt)), verbose)
-    dig = _digest()
-    if not force and os.path.isfile(LIB) and os.path.isfile(STAMP) and open(STAMP).read().strip() == dig:
-        return LIB
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.isfile(hipcc):
-        hipcc = "hipcc"
-    objs = []
-    procs = []
-    os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
-    for src in sources():
-        obj = os.path.join(HERE, "build", os.path.basename(src) + ".o")
-        cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
-               "-I" + CSRC] + _extra_flags() + PER_FILE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
-        objs.append(obj)
-    for src, pr in procs:
-        out, _ = pr.communicate()
-        if pr.returncode != 0:
-            sys.stderr.write(out.decode(errors="replace"))
-            raise RuntimeError(f"hipcc failed on {src}")
-    cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB] + objs
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    if res.returncode != 0:
-        sys.stderr.write(res.stdout.decode(errors="replace"))
-        raise RuntimeError("link of libe4s_hip.so failed")
-    with open(STAMP, "w") as fh:
-        fh.write(dig)
-    return LIB
-
-
-def _build_to(lib, objdir, verbose=False):
+def _compile_and_link(lib, objdir, verbose):
+    """Every source to an object under objdir (all hipcc processes at once), then one shared library."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if not os.path.isfile(hipcc):
         hipcc = "hipcc"
@@ -88,8 +51,8 @@ def _build_to(lib, objdir, verbose=False):
     procs, objs = [], []
     for src in sources():
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
-        cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC] + \
-            _extra_flags() + PER_FILE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
+        cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
+               "-I" + CSRC] + _extra_flags() + PER_FILE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
@@ -102,8 +65,28 @@ def _build_to(lib, objdir, verbose=False):
     res = subprocess.run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib] + objs, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     if res.returncode != 0:
         sys.stderr.write(res.stdout.decode(errors="replace"))
-        raise RuntimeError("link failed")
+        raise RuntimeError(f"link of {os.path.basename(lib)} failed")
     return lib
+
+
+def build(force=False, verbose=False):
+    """Compile every HIP source for gfx950 and link libe4s_hip.so in-tree.  Returns the path.
+    E4S_BUILD_OUT=<path.so>: a SECOND library beside the product one (profiling builds with E4S_BUILD_ABLATIONS=1, A/B builds; loaded
+    with E4S_LIB_PATH): own object directory, no stamp, the product library is not touched."""
+    alt = os.environ.get("E4S_BUILD_OUT")
+    if alt:
+        return _build_to(os.path.abspath(alt), os.path.join(os.path.dirname(os.path.abspath(alt)), "obj_" + os.path.basename(alt)), verbose)
+    dig = _digest()
+    if not force and os.path.isfile(LIB) and os.path.isfile(STAMP) and open(STAMP).read().strip() == dig:
+        return LIB
+    _compile_and_link(LIB, os.path.join(HERE, "build"), verbose)
+    with open(STAMP, "w") as fh:
+        fh.write(dig)
+    return LIB
+
+
+def _build_to(lib, objdir, verbose=False):
+    return _compile_and_link(lib, objdir, verbose)
 
 
 if __name__ == "__main__":

@@ -19,15 +19,11 @@
 // (row >> 1) & 7 instead of 144-byte padded rows (A 41 KB, B 36 KB), the output staging tile aliased over the halo buffer (one more
 // barrier per tile), four waves of 64 pixels (two accumulators; 6 fragment reads per 6 MFMAs instead of 4 per 3): 79 KB per block.
 // Arithmetic as conv_bf16x3.hip: three v_mfma_f32_32x32x16_bf16 per product on hi/lo-split fp32 operands, fp32 accumulate.
-#include "common.h"
+#include "mfma_rows.h"                                          // the swizzled [32 hi | 32 lo] row (swz, swz_halo and their bank analysis)
 #include <stdlib.h>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-
-constexpr int KC = 32, ROWB = 128, LO = 64;                                     // [32 hi | 32 lo] bf16 per row, swizzled (swz below)
 constexpr int TW = 16, TH = 16, HALO_W = TW + 2, HALO = (TH + 2) * HALO_W;      // 16 x 16-pixel tiles, 324 halo pixels
 constexpr int BM = TH * TW, BN = 32, NTHR = 256;                                // 4 waves x (64 pixels x 32 channels)
 constexpr int ITEMS = HALO * 4, AJ = (ITEMS + NTHR - 1) / NTHR;                 // 1296 items, 6 per thread
@@ -38,30 +34,6 @@ constexpr int SMEM = B_BYTES + A_BYTES + BM * 8 + 3 * BN * 4;                   
 static_assert(BPIECES % NTHR == 0 && BM == NTHR, "thread layout");
 static_assert(BM * YLD * 4 <= A_BYTES, "the output staging tile aliases the halo buffer");
 static_assert(2 * SMEM <= 160 * 1024, "two blocks per CU");
-
-// byte offset of 16-byte granule g (0..3: 8 hi channels each, 4..7: the lo halves) of row r; the lo half of a granule is the same
-// offset ^ 64, the second k-step ^ 32.  A ds_read_b128 is served in groups of 16 lanes ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ...)
-// that must hit 16 different 16-byte slots of the 256-byte bank line.  Weights: a group reads 16 rows of one tap at one logical granule;
-// rows of one parity share a 128-byte half and have eight different (r >> 1) & 7 -- conflict free.  Halo: a group's pixels are columns
-// x0 .. x0 + 15 of TWO image rows ({0-3, 12-15} of one, {4-11} of the next), so the swizzle keys on the halo COLUMN hx = r % 18 (the row
-// pitch is even: a row's parity is its column's): (hx & 1, (hx >> 1) & 7) takes 16 different values -- conflict free (keyed on r itself,
-// like the 144-byte padded rows of round 3, every group was 2-way: the 30.9 % of conflict cycles in r04f's counters).
-__device__ __forceinline__ int swz(int r, int g) { return r * ROWB + ((g ^ ((r >> 1) & 7)) << 4); }
-__device__ __forceinline__ int swz_halo(int h, int g) { return h * ROWB + ((g ^ (((h % HALO_W) >> 1) & 7)) << 4); }
-
-__device__ __forceinline__ void split_store(unsigned char* base, int off, const f32x8 v) {
-    const bf16x8 h = __builtin_convertvector(v, bf16x8);
-    const f32x8 r = v - __builtin_convertvector(h, f32x8);
-    const bf16x8 l = __builtin_convertvector(r, bf16x8);
-    *reinterpret_cast<bf16x8*>(base + off) = h;
-    *reinterpret_cast<bf16x8*>(base + (off ^ LO)) = l;
-}
-
-__device__ __forceinline__ f32x8 load8(const float* src) {
-    const f32x4 lo4 = *reinterpret_cast<const f32x4*>(src);
-    const f32x4 hi4 = *reinterpret_cast<const f32x4*>(src + 4);
-    return f32x8{lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-}
 
 struct TileId { int tb, tyb, txb, nt; };
 
@@ -133,7 +105,7 @@ __global__ __launch_bounds__(NTHR, 2) void conv_c32_kernel(const e4s_conv_params
                 f32x8 v = R.a[j];
                 if (XF) v = v * R.sc;
                 if (!R.ok[j]) v = zero8;
-                split_store(sA, swz_halo(item >> 2, item & 3), v);
+                split_store(sA, swz_halo<HALO_W>(item >> 2, item & 3), v);
             }
         }
     };
@@ -162,7 +134,7 @@ __global__ __launch_bounds__(NTHR, 2) void conv_c32_kernel(const e4s_conv_params
         const int m_row = wave * 64 + tm * 32 + li;
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap)
-            ro[tm][tap] = swz_halo((m_row / TW + tap / 3) * HALO_W + (m_row % TW) + tap % 3, kh);
+            ro[tm][tap] = swz_halo<HALO_W>((m_row / TW + tap / 3) * HALO_W + (m_row % TW) + tap % 3, kh);
     }
     const int brow = swz(li, kh);                               // + tap * BN * ROWB (a multiple of 16 rows: the swizzle term is the row's own)
 

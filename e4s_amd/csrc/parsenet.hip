@@ -9,257 +9,40 @@
 //   epilogue v = acc * scale[c] + bias[c] (eval-mode BatchNorm folded on the host; either may be NULL), then optional LeakyReLU,
 //            then optional + r0, then optional + r1 (NHWC maps at the output resolution: a block's identity + res, and the net's
 //            feat + body(feat) on the last body block)
-// A block computes 32 output channels of its pixel tile (blockIdx.y picks the 32); four waves own a quarter of the pixels each as 32-row
-// MFMA tiles.  The input channels go by in chunks of 32: per chunk the halo (128 bytes per pixel) and the chunk's 9 x 32 x 32 weights
-// (36 KB, pre-packed by e4s_pconv_pack_f32) are staged in LDS while the next chunk's global loads are in flight in registers.  LDS
-// rows are 128 bytes with the 16-byte granule XOR-swizzled (csrc/conv_c32.hip).  Arithmetic: split-bf16 (rows hold [32 hi | 32 lo]
-// bf16; three v_mfma_f32_32x32x16_bf16 per product, lo x hi first, fp32 accumulate) or exact fp32 (v_mfma_f32_32x32x2_f32) -- the
-// same tile code.  The summation order of an output is fixed (chunk, tap, k-step): its bits do not depend on the batch or on the
-// tile's place.  Tiles that overhang the image are masked.
+// The kernel is the shared halo-tile kernel of halo_conv3x3.h (reflect padding, blockIdx.y picks 32 of the Cout channels, weights pre-packed
+// by e4s_pconv_pack_f32): its tiles, LDS layout, arithmetic (split-bf16 or exact fp32) and fixed summation order are described there.
 //
 // Head: the encoder's first conv (3 -> Cout <= 64) straight from uint8 HWC pixels (x / 255 * 2 - 1 as face_parsing.py:59-63 computes
 //       it, in double, optional BGR <-> RGB flip) or an fp32 NCHW image; reflect pad, + bias.
 // Tail: out_mask_conv (Cin <= 64 -> 19), reflect pad, + bias, fused with the argmax over classes (first maximum, as torch.argmax) and
 //       the MASK_COLORMAP lookup of face_parsing.py:30 (classes 0, 14 and 18 -> 0, every other -> 255).
-#include "common.h"
+#include "halo_conv3x3.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-
-constexpr int KC = 32, ROWB = 128, LO = 64;                                     // one 32-channel chunk per 128-byte LDS row
-constexpr int BN = 32, NTHR = 256, TW = 16;
-constexpr int BPIECES = 9 * BN * 8, BJ = BPIECES / NTHR;                        // 2304 16-byte pieces, 9 per thread and chunk
-constexpr int B_BYTES = 9 * BN * ROWB;                                          // 36 864
-constexpr int YLD = 36;                                                         // floats per pixel row of the output staging tile
-static_assert(BPIECES % NTHR == 0, "thread layout");
-
-template <int S>
-struct Tile {
-    static constexpr int TH = S == 2 ? 8 : 16;
-    static constexpr int BM = TH * TW, TM = BM / 128;                           // 256 / 128 pixels; 2 / 1 MFMA row tiles per wave
-    static constexpr int HALO_H = (TH - 1) * S + 3, HALO_W = (TW - 1) * S + 3;  // 18 x 18 / 17 x 33
-    static constexpr int HALO = HALO_H * HALO_W;                                // 324 / 561 halo pixels
-    static constexpr int ITEMS = HALO * 4, AJ = (ITEMS + NTHR - 1) / NTHR;      // 8-channel items: 6 / 9 per thread
-    static constexpr int A_BYTES = HALO * ROWB;                                 // 41 472 / 71 808
-    static constexpr int SMEM = B_BYTES + A_BYTES + BM * 4;                     // 79 360 (two blocks per CU) / 109 184 (one)
-    static constexpr int OCC = 2 * SMEM <= 160 * 1024 ? 2 : 1;
-    static_assert(BM * YLD * 4 <= A_BYTES, "the output staging tile aliases the halo buffer");
-    static_assert(SMEM <= 160 * 1024, "LDS of one CU");
+// v = acc * scale[c] + bias[c] (either NULL: 1 and 0), optional LeakyReLU, then r0 + v, then r1 + v (either NULL: skipped)
+struct PconvEpi {
+    const float* scale;
+    const float* bias;
+    const float* r0;
+    const float* r1;
+    int r0_cstride, r1_cstride, lrelu;
+    float slope;
+    struct Chan { float scale, bias; };
+    __device__ __forceinline__ Chan chan(int c) const { return {scale ? scale[c] : 1.f, bias ? bias[c] : 0.f}; }
+    __device__ __forceinline__ float point(float acc, Chan k) const {
+        float v = acc * k.scale + k.bias;
+        if (lrelu) v = v > 0.f ? v : v * slope;
+        return v;
+    }
+    __device__ __forceinline__ f32x4 store(f32x4 v, size_t off, int c) const {
+        if (r0) v = *reinterpret_cast<const f32x4*>(r0 + off * r0_cstride + c) + v;
+        if (r1) v = *reinterpret_cast<const f32x4*>(r1 + off * r1_cstride + c) + v;
+        return v;
+    }
 };
-
-// byte offset of 16-byte granule g (0..7) of row r.  split-bf16: granules 0..3 hold 8 hi channels each, g + 4 (offset ^ 64) their lo
-// halves; fp32: granule g holds channels 4 g .. 4 g + 3.  Weight rows key the swizzle on the row, halo rows on the halo column.
-__device__ __forceinline__ int swz(int r, int g) { return r * ROWB + ((g ^ ((r >> 1) & 7)) << 4); }
-template <int HALO_W>
-__device__ __forceinline__ int swz_halo(int h, int g) { return h * ROWB + ((g ^ (((h % HALO_W) >> 1) & 7)) << 4); }
-
-__device__ __forceinline__ void split_store(unsigned char* base, int off, const f32x8 v) {
-    const bf16x8 h = __builtin_convertvector(v, bf16x8);
-    const f32x8 r = v - __builtin_convertvector(h, f32x8);
-    const bf16x8 l = __builtin_convertvector(r, bf16x8);
-    *reinterpret_cast<bf16x8*>(base + off) = h;
-    *reinterpret_cast<bf16x8*>(base + (off ^ LO)) = l;
-}
-
-__device__ __forceinline__ f32x8 load8(const float* src) {
-    const f32x4 lo4 = *reinterpret_cast<const f32x4*>(src);
-    const f32x4 hi4 = *reinterpret_cast<const f32x4*>(src + 4);
-    return f32x8{lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-}
-
-// ReflectionPad2d(1) on a grid of n >= 2 positions: -1 -> 1, n -> n - 2 (g is in [-1, n])
-__device__ __forceinline__ int reflect1(int g, int n) { return g < 0 ? -g : (g >= n ? 2 * n - 2 - g : g); }
-
-// F32: 1 = exact fp32 MFMA, 0 = split-bf16; S: stride; UP2: 1 = the grid is the nearest x2 upsampling of x [B,Hi,Wi,..]
-template <int F32, int S, int UP2>
-__global__ __launch_bounds__(NTHR, Tile<S>::OCC) void pconv_kernel(const e4s_pconv_params p, const int Ho, const int Wo, const int tx_n,
-                                                                   const int per_img) {
-    typedef Tile<S> T;
-    constexpr int TH = T::TH, BM = T::BM, TM = T::TM, HALO_W = T::HALO_W, ITEMS = T::ITEMS, AJ = T::AJ, A_BYTES = T::A_BYTES;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* sB = smem;                                   // [9][32][ROWB]  weights of the current chunk
-    unsigned char* sA = smem + B_BYTES;                         // [HALO][ROWB]   halo of the current chunk
-    float* sY = reinterpret_cast<float*>(sA);                   // [BM][YLD]      output staging tile (aliases the halo)
-    int* s_out = reinterpret_cast<int*>(sA + A_BYTES);          // [BM] output pixel index or -1
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, kh = lane >> 5;
-    const int Hg = UP2 ? 2 * p.Hi : p.Hi, Wg = UP2 ? 2 * p.Wi : p.Wi;          // the grid the reflect map applies on
-    const int tb = blockIdx.x / per_img;
-    const int rem = blockIdx.x - tb * per_img;
-    const int tyb = rem / tx_n, txb = rem - tyb * tx_n;
-    const int cb = blockIdx.y;                                  // output channels 32 cb .. 32 cb + 31
-    const int nchunk = p.Cin / KC;
-
-    // this thread's halo items: (halo pixel, 8-channel group) -> offset of channel group 0 of the source pixel, the same for every
-    // chunk.  Grid positions past the reflected border (-1 and n) belong to no live output and stay zero.
-    size_t aoff[AJ];
-    bool aok[AJ];
-#pragma unroll
-    for (int j = 0; j < AJ; ++j) {
-        const int item = tid + NTHR * j;
-        const int h = item >> 2, q = item & 3;
-        const int hy = h / HALO_W, hx = h - hy * HALO_W;
-        const int gy = tyb * TH * S + hy - 1, gx = txb * TW * S + hx - 1;
-        aok[j] = item < ITEMS && gy <= Hg && gx <= Wg;
-        const int ry = reflect1(gy, Hg), rx = reflect1(gx, Wg);
-        const int iy = UP2 ? ry >> 1 : ry, ix = UP2 ? rx >> 1 : rx;
-        aoff[j] = aok[j] ? (((size_t)tb * p.Hi + iy) * p.Wi + ix) * p.x_cstride + q * 8 : 0;
-    }
-    const f32x8 zero8 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    f32x8 ra[AJ];
-    f32x4 rb[BJ];
-    const unsigned char* wbase = reinterpret_cast<const unsigned char*>(p.w) + (size_t)cb * nchunk * B_BYTES;
-    auto fetch = [&](int chunk) {
-#pragma unroll
-        for (int j = 0; j < AJ; ++j) ra[j] = aok[j] ? load8(p.x + aoff[j] + chunk * KC) : zero8;
-        const unsigned char* wb = wbase + (size_t)chunk * B_BYTES;
-#pragma unroll
-        for (int j = 0; j < BJ; ++j) rb[j] = *reinterpret_cast<const f32x4*>(wb + (size_t)(tid + NTHR * j) * 16);
-    };
-    auto stage = [&]() {
-#pragma unroll
-        for (int j = 0; j < AJ; ++j) {
-            const int item = tid + NTHR * j;
-            if (item < ITEMS) {
-                if (F32) {
-                    *reinterpret_cast<f32x4*>(sA + swz_halo<HALO_W>(item >> 2, 2 * (item & 3))) = f32x4{ra[j][0], ra[j][1], ra[j][2], ra[j][3]};
-                    *reinterpret_cast<f32x4*>(sA + swz_halo<HALO_W>(item >> 2, 2 * (item & 3) + 1)) =
-                        f32x4{ra[j][4], ra[j][5], ra[j][6], ra[j][7]};
-                } else {
-                    split_store(sA, swz_halo<HALO_W>(item >> 2, item & 3), ra[j]);
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < BJ; ++j) {
-            const int i = tid + NTHR * j;
-            *reinterpret_cast<f32x4*>(sB + swz(i >> 3, i & 7)) = rb[j];
-        }
-    };
-
-    if (tid < BM) {
-        const int ay = tyb * TH + tid / TW, ax = txb * TW + tid % TW;
-        s_out[tid] = (ay < Ho && ax < Wo) ? (tb * Ho + ay) * Wo + ax : -1;
-    }
-    // fragment rows: wave w owns pixels 32 TM w .. 32 TM (w + 1) - 1 of the tile as TM 32-row MFMA tiles; ro[tm][tap] = byte offset of
-    // (halo row of the pixel's window shifted by the tap, granule kh); further granules are XORs of the offset
-    int ro[TM][9];
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm) {
-        const int m_row = (wave * TM + tm) * 32 + li;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap)
-            ro[tm][tap] = swz_halo<HALO_W>(((m_row / TW) * S + tap / 3) * HALO_W + (m_row % TW) * S + tap % 3, kh);
-    }
-    const int brow = swz(li, kh);                               // + tap * BN * ROWB (a multiple of 16 rows: the swizzle term is the row's own)
-
-    f32x16 acc[TM];
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[tm][r] = 0.f;
-
-    fetch(0);
-    for (int chunk = 0; chunk < nchunk; ++chunk) {
-        __syncthreads();                                        // every reader of the previous chunk's LDS image is done
-        stage();
-        if (chunk + 1 < nchunk) fetch(chunk + 1);
-        __syncthreads();
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const unsigned char* Bt = sB + tap * (BN * ROWB);
-            if (F32) {
-                // lane (li, kh) holds channels 4 (2 gp + kh) + s of its row, for A and B alike: k-step (gp, s) contracts channels
-                // 8 gp + s and 8 gp + 4 + s
-#pragma unroll
-                for (int gp = 0; gp < 4; ++gp) {
-                    const f32x4 b4 = *reinterpret_cast<const f32x4*>(Bt + (brow ^ (gp * 32)));
-                    f32x4 a4[TM];
-#pragma unroll
-                    for (int tm = 0; tm < TM; ++tm) a4[tm] = *reinterpret_cast<const f32x4*>(sA + (ro[tm][tap] ^ (gp * 32)));
-#pragma unroll
-                    for (int s = 0; s < 4; ++s)
-#pragma unroll
-                        for (int tm = 0; tm < TM; ++tm) acc[tm] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[tm][s], b4[s], acc[tm], 0, 0, 0);
-                }
-            } else {
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    const bf16x8 bh = *reinterpret_cast<const bf16x8*>(Bt + (brow ^ (kk * 32)));
-                    const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Bt + (brow ^ (kk * 32) ^ LO));
-                    bf16x8 ah[TM], al[TM];
-#pragma unroll
-                    for (int tm = 0; tm < TM; ++tm) {
-                        ah[tm] = *reinterpret_cast<const bf16x8*>(sA + (ro[tm][tap] ^ (kk * 32)));
-                        al[tm] = *reinterpret_cast<const bf16x8*>(sA + (ro[tm][tap] ^ (kk * 32) ^ LO));
-                    }
-#pragma unroll
-                    for (int tm = 0; tm < TM; ++tm) acc[tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[tm], bh, acc[tm], 0, 0, 0);
-#pragma unroll
-                    for (int tm = 0; tm < TM; ++tm) acc[tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bl, acc[tm], 0, 0, 0);
-#pragma unroll
-                    for (int tm = 0; tm < TM; ++tm) acc[tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bh, acc[tm], 0, 0, 0);
-                }
-            }
-        }
-    }
-
-    // ---- epilogue: scale, bias and LeakyReLU into the LDS staging tile, then 16-byte stores, 8 lanes per pixel's 128-byte slice ----
-    const int co = cb * BN;
-    const float scv = p.scale ? p.scale[co + li] : 1.f;
-    const float bsv = p.bias ? p.bias[co + li] : 0.f;
-    __syncthreads();                                            // every wave is through with the halo: sY may overwrite it
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (wave * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-            float v = acc[tm][r] * scv + bsv;
-            if (p.lrelu) v = v > 0.f ? v : v * p.slope;
-            sY[row * YLD + li] = v;
-        }
-    __syncthreads();
-    const int c4 = tid & 7;
-#pragma unroll
-    for (int ps = 0; ps < BM / (NTHR / 8); ++ps) {
-        const int px = ps * (NTHR / 8) + (tid >> 3);
-        const int off = s_out[px];
-        if (off < 0) continue;
-        f32x4 v = *reinterpret_cast<const f32x4*>(sY + px * YLD + c4 * 4);
-        if (p.r0) v = *reinterpret_cast<const f32x4*>(p.r0 + (size_t)off * p.r0_cstride + co + c4 * 4) + v;
-        if (p.r1) v = *reinterpret_cast<const f32x4*>(p.r1 + (size_t)off * p.r1_cstride + co + c4 * 4) + v;
-        *reinterpret_cast<f32x4*>(p.y + (size_t)off * p.y_cstride + co + c4 * 4) = v;
-    }
-}
-
-// w [Cout][Cin][3][3] -> [Cout / 32][Cin / 32][9][32 co][128 bytes]: 32 floats (SPLIT = 0) or [32 hi | 32 lo] bf16 (SPLIT = 1)
-template <int SPLIT>
-__global__ void pconv_pack_kernel(const float* __restrict__ w, unsigned char* __restrict__ out, int Cin, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int ci = (int)(i & 31), co = (int)((i >> 5) & 31);
-    const int64_t rest = i >> 10;
-    const int nchunk = Cin / KC;
-    const int tap = (int)(rest % 9);
-    const int64_t cc = rest / 9;
-    const int chunk = (int)(cc % nchunk), cb = (int)(cc / nchunk);
-    const float v = w[((size_t)(cb * BN + co) * Cin + chunk * KC + ci) * 9 + tap];
-    unsigned char* row = out + (size_t)(i >> 5) * ROWB;
-    if (SPLIT) {
-        const __bf16 h = (__bf16)v;
-        const __bf16 l = (__bf16)(v - (float)h);
-        reinterpret_cast<__bf16*>(row)[ci] = h;
-        reinterpret_cast<__bf16*>(row + LO)[ci] = l;
-    } else {
-        reinterpret_cast<float*>(row)[ci] = v;
-    }
-}
 
 constexpr int HEAD_CMAX = 64;
 
@@ -360,20 +143,11 @@ __global__ __launch_bounds__(256) void parsenet_tail_kernel(const float* __restr
     if (mask) mask[pix] = (best == 0 || best == 14 || best == 18) ? 0 : 255;
 }
 
-bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 template <int F32, int S, int UP2>
 int launch(const e4s_pconv_params& p, int Ho, int Wo, hipStream_t st) {
-    typedef Tile<S> T;
-    auto kern = pconv_kernel<F32, S, UP2>;
-    static std::atomic<uint64_t> smem_set{0};
-    if (int e = e4s_ensure_dyn_smem(reinterpret_cast<const void*>(kern), T::SMEM, smem_set)) return e;
-    const int tx_n = (Wo + TW - 1) / TW, per_img = ((Ho + T::TH - 1) / T::TH) * tx_n;
-    const int64_t ntiles = (int64_t)p.B * per_img;
-    if (ntiles >= (1ll << 31) || p.Cout / BN > 65535) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles, (unsigned)(p.Cout / BN)), dim3(NTHR), T::SMEM, st, p, Ho, Wo, tx_n, per_img);
-    E4S_CHECK_LAUNCH();
-    return 0;
+    const HaloConvArgs a = {p.x, p.w, p.y, p.B, p.Hi, p.Wi, p.Cin, p.x_cstride, p.y_cstride, 0};
+    const PconvEpi epi = {p.scale, p.bias, p.r0, p.r1, p.r0_cstride, p.r1_cstride, p.lrelu, p.slope};
+    return halo_conv3x3_launch<F32, S, UP2, ReflectPad>(a, epi, Ho, Wo, p.Cout, st);
 }
 
 // output size of reflect pad 1 + 3x3 at the given stride on a grid of n (2 n with up2) positions; 0: a grid below 2 cannot be reflected
@@ -411,18 +185,11 @@ extern "C" int e4s_pconv_f32(const e4s_pconv_params* pp, void* stream) {
     return p.up2 ? launch<0, 1, 1>(p, Ho, Wo, st) : launch<0, 1, 0>(p, Ho, Wo, st);
 }
 
-extern "C" int64_t e4s_pconv_pack_bytes(int Cin, int Cout) {
-    return Cin >= KC && Cin % KC == 0 && Cout >= BN && Cout % BN == 0 ? (int64_t)(Cout / BN) * (Cin / KC) * B_BYTES : 0;
-}
+extern "C" int64_t e4s_pconv_pack_bytes(int Cin, int Cout) { return halo_conv3x3_pack_bytes(Cin, Cout); }
 
 extern "C" int e4s_pconv_pack_f32(const float* w, void* out, int Cin, int Cout, int split, void* stream) {
     if (!w || !out || !aligned16(out) || e4s_pconv_pack_bytes(Cin, Cout) == 0) return (int)hipErrorInvalidValue;
-    const int64_t n = (int64_t)(Cout / BN) * (Cin / KC) * 9 * BN * KC;
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (split) hipLaunchKernelGGL(pconv_pack_kernel<1>, grid, dim3(256), 0, as_stream(stream), w, static_cast<unsigned char*>(out), Cin, n);
-    else hipLaunchKernelGGL(pconv_pack_kernel<0>, grid, dim3(256), 0, as_stream(stream), w, static_cast<unsigned char*>(out), Cin, n);
-    E4S_CHECK_LAUNCH();
-    return 0;
+    return halo_conv3x3_pack(w, out, Cin, Cout, split, as_stream(stream));
 }
 
 extern "C" int e4s_parsenet_head_f32(const void* src, int is_u8, int flip, const float* wp, const float* bias, float* y, int Cout, int B,

@@ -22,35 +22,14 @@
 // Select: score > threshold on the score-sorted list (ties: lower prior index first, from a stable sort), the top_k cut, greedy NMS
 //         as py_cpu_nms.py:18-36 (+ 1 areas, suppression when not ovr <= thresh), keep_top_k, the landmark re-layout to five x then
 //         five y and the final / ss.  One block per image; fixed-capacity outputs and a device count.
-#include "common.h"
+#include "mfma_rows.h"                                          // the swizzled 128-byte row (swz and its bank analysis)
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-
-constexpr int KC = 32, ROWB = 128, LO = 64, BM = 128, NTHR = 256, YLD = 36, PB = 64;
+constexpr int BM = 128, NTHR = 256, YLD = 36, PB = 64;
 constexpr int A_BYTES = BM * ROWB;                                              // 16 384
-
-// byte offset of 16-byte granule g (0..7) of row r.  split-bf16: granules 0..3 hold 8 hi channels each, g + 4 (offset ^ 64) their lo
-// halves; fp32: granule g holds channels 4 g .. 4 g + 3.
-__device__ __forceinline__ int swz(int r, int g) { return r * ROWB + ((g ^ ((r >> 1) & 7)) << 4); }
-
-__device__ __forceinline__ void split_store(unsigned char* base, int off, const f32x8 v) {
-    const bf16x8 h = __builtin_convertvector(v, bf16x8);
-    const f32x8 r = v - __builtin_convertvector(h, f32x8);
-    const bf16x8 l = __builtin_convertvector(r, bf16x8);
-    *reinterpret_cast<bf16x8*>(base + off) = h;
-    *reinterpret_cast<bf16x8*>(base + (off ^ LO)) = l;
-}
-
-__device__ __forceinline__ f32x8 load8(const float* src) {
-    const f32x4 lo4 = *reinterpret_cast<const f32x4*>(src);
-    const f32x4 hi4 = *reinterpret_cast<const f32x4*>(src + 4);
-    return f32x8{lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-}
 
 // ATen's nearest source index (UpSample.h nearest_neighbor_compute_source_index): float scale, floorf, clamp
 __device__ __forceinline__ int nearest_src(int dst, int in, int out) {
@@ -255,15 +234,7 @@ __global__ void rconv_pack_kernel(const float* __restrict__ w, unsigned char* __
     const int tap = (int)(rest % ntaps);
     const int cb = (int)(rest / ntaps);
     const float v = w[((size_t)(cb * 64 + co) * Cin + chunk * KC + ci) * ntaps + tap];
-    unsigned char* row = out + (size_t)(i >> 5) * ROWB;
-    if (SPLIT) {
-        const __bf16 h = (__bf16)v;
-        const __bf16 l = (__bf16)(v - (float)h);
-        reinterpret_cast<__bf16*>(row)[ci] = h;
-        reinterpret_cast<__bf16*>(row + LO)[ci] = l;
-    } else {
-        reinterpret_cast<float*>(row)[ci] = v;
-    }
+    pack_row_store<SPLIT>(out + (size_t)(i >> 5) * ROWB, ci, v);
 }
 
 // ---- prep: uint8 BGR HWC -> fp32 NHWC minus the channel means, optionally through a half-pixel bilinear shrink ----
@@ -471,8 +442,6 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ b
         else lm_out[((size_t)b * K + r) * 10 + (c - 5)] = v;
     }
 }
-
-bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 int rconv_out(int n, int k, int stride) { return (n + 2 * (k / 2) - k) / stride + 1; }
 
