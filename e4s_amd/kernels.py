@@ -1994,3 +1994,148 @@ def merge_blend(masks, faces, bg, out=None):
     call("e4s_merge_blend_u8", fptr(masks.contiguous()) if n else None, ptr(faces.contiguous()) if n else None, ptr(bg), ptr(out), n, h, w,
          stream())
     return out
+
+
+# ---- face-vid2vid keypoints and head pose (reenact.py) -----------------------------------------
+def conv3d_pack(w, f32):
+    """nn.Conv3d weight [Cout,Cin,3,3,3] (Cin % 32 == 0, any Cout) -> the opaque image e4s_conv3d_f32 reads (Cout padded to 32)."""
+    w = _f32(w)
+    if w.dim() != 5 or tuple(w.shape[2:]) != (3, 3, 3):
+        raise RuntimeError(f"conv3d_pack: a [Cout, 32k, 3, 3, 3] weight, got {tuple(w.shape)}")
+    cout, cin = w.shape[:2]
+    nbytes = lib.load().e4s_conv3d_pack_bytes(cin, cout)
+    if nbytes == 0:
+        raise RuntimeError(f"conv3d_pack: a [Cout, 32k, 3, 3, 3] weight, got {tuple(w.shape)}")
+    out = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
+    call("e4s_conv3d_pack_f32", fptr(w), ptr(out), cin, cout, 0 if f32 else 1, stream())
+    out.conv3d_f32 = bool(f32)                                               # conv3d refuses a pack of the other precision
+    out.conv3d_shape = (cout, cin)
+    return out
+
+
+def conv3d(x, w_pack, cout, y, *, bias=None, relu=False, up2=False, f32=None):
+    """Zero-padded 3x3x3 conv: x fp32 [B,D,H,W,Cin] with contiguous channels (any other strides: a permuted view is read in place)
+    -> the first cout channels of the contiguous y [B,D,Ho,Wo,C].  up2: x is read through the nearest (1, 2, 2) up-sampling.
+    v = acc + bias, ReLU with relu.  Writes y in place and returns it."""
+    if x.dtype != torch.float32 or x.dim() != 5 or not x.is_cuda or x.stride(4) != 1:
+        raise RuntimeError("conv3d: x is an fp32 device volume [B,D,H,W,C] with contiguous channels")
+    b, d, hi, wi, cin = x.shape
+    ho, wo = (2 * hi, 2 * wi) if up2 else (hi, wi)
+    if y.dtype != torch.float32 or y.dim() != 5 or not y.is_contiguous() or tuple(y.shape[:4]) != (b, d, ho, wo) or y.shape[4] < cout:
+        raise RuntimeError(f"conv3d: y is a contiguous fp32 volume of {(b, d, ho, wo)} voxels and {cout} or more channels, got {tuple(y.shape)}")
+    f32 = sr_f32() if f32 is None else bool(f32)
+    if getattr(w_pack, "conv3d_shape", None) != (cout, cin) or getattr(w_pack, "conv3d_f32", None) != f32:
+        raise RuntimeError(f"conv3d: w_pack is not conv3d_pack's image of a [{cout},{cin},3,3,3] weight in this precision")
+    for name, t in (("w_pack", w_pack), ("y", y), ("bias", bias)):
+        if t is not None and t.device != x.device:
+            raise RuntimeError(f"conv3d: {name} is on {t.device}, x on {x.device}")
+    p = lib.Conv3dParams()
+    p.x, p.w, p.y = c_p(x.data_ptr()), fptr(w_pack), fptr(y)
+    if bias is not None:
+        if bias.numel() != cout:
+            raise RuntimeError(f"conv3d: bias has {bias.numel()} entries for {cout} channels")
+        p.bias = fptr(_f32(bias))
+    p.x_bstride, p.x_dstride, p.x_ystride, p.x_xstride = x.stride(0), x.stride(1), x.stride(2), x.stride(3)
+    p.B, p.D, p.Hi, p.Wi, p.Cin, p.Cout = b, d, hi, wi, cin, cout
+    p.y_cstride = y.shape[4]
+    p.up2, p.relu, p.precision = 1 if up2 else 0, 1 if relu else 0, 1 if f32 else 0
+    call("e4s_conv3d_f32", ctypes.byref(p), stream())
+    return y
+
+
+def softargmax3d(logits, temperature, jac=None, channels_last=False, value=None, jacobian=None):
+    """KPDetector's head.  logits fp32 [B,K,D,H,W] (or, channels_last, [B,D,H,W,K]); jac: the jacobian maps [B,J*9,D,H,W] (or
+    [B,D,H,W,J*9]), J = K or 1 -> (value [B,K,3], jacobian [B,K,3,3] or None).  Sums are taken in an order fixed by (D, H, W)."""
+    def strides(t, what):
+        if t.dtype != torch.float32 or t.dim() != 5 or not t.is_contiguous() or not t.is_cuda:
+            raise RuntimeError(f"softargmax3d: {what} is a contiguous fp32 5-D device tensor")
+        if channels_last:
+            b, d, h, w, c = t.shape
+            return (b, c, d, h, w), (d * h * w * c, 1, c)
+        b, c, d, h, w = t.shape
+        return (b, c, d, h, w), (c * d * h * w, d * h * w, 1)
+    (b, k, d, h, w), ls = strides(logits, "logits")
+    dev = logits.device
+    value = torch.empty(b, k, 3, device=dev, dtype=torch.float32) if value is None else value
+    js, nj = (0, 0, 0), 0
+    if jac is not None:
+        (jb, jc, jd, jh, jw), js = strides(jac, "jac")
+        if (jb, jd, jh, jw) != (b, d, h, w) or jc not in (9, 9 * k):
+            raise RuntimeError(f"softargmax3d: jac holds 9 or {9 * k} maps of the logits' volume, got {tuple(jac.shape)}")
+        nj = jc // 9
+        jacobian = torch.empty(b, k, 3, 3, device=dev, dtype=torch.float32) if jacobian is None else jacobian
+    else:
+        jacobian = None
+    call("e4s_softargmax3d_f32", fptr(logits), ls[0], ls[1], ls[2], fptr(jac), js[0], js[1], js[2], nj, b, k, d, h, w, float(temperature),
+         fptr(value), fptr(jacobian), stream())
+    return value, jacobian
+
+
+def aa_down(frames, taps, step, out=None):
+    """AntiAliasInterpolation2d at the kept positions: frames [B,H,W,3] fp32 or uint8 (read as x / 255), taps: odd-length fp32 device
+    vector of the normalised 1-D Gaussian -> fp32 [B,ceil(H/step),ceil(W/step),3].  One tap of 1.0 at step 1 converts a frame."""
+    if frames.dtype not in (torch.float32, torch.uint8) or frames.dim() != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise RuntimeError("aa_down: contiguous fp32 or uint8 frames [B,H,W,3]")
+    b, h, w, _ = frames.shape
+    ho, wo = -(-h // step), -(-w // step)
+    out = torch.empty(b, ho, wo, 3, device=frames.device, dtype=torch.float32) if out is None else out
+    if tuple(out.shape) != (b, ho, wo, 3) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise RuntimeError(f"aa_down: out is a contiguous fp32 buffer {(b, ho, wo, 3)}")
+    call("e4s_aa_down_f32", ptr(frames), 1 if frames.dtype == torch.uint8 else 0, fptr(out), b, h, w, fptr(taps), taps.numel(), int(step),
+         stream())
+    return out
+
+
+def avgpool2(x, y=None):
+    """nn.AvgPool2d(2) of NHWC x -> [B,H/2,W/2,C] (odd sizes drop the last row / column)."""
+    b, hi, wi, c = x.shape
+    y = torch.empty(b, hi // 2, wi // 2, c, device=x.device, dtype=torch.float32) if y is None else y
+    if tuple(y.shape) != (b, hi // 2, wi // 2, c) or not y.is_contiguous():
+        raise RuntimeError("avgpool2: y holds the floored half-size output of x")
+    call("e4s_avgpool2_f32", fptr(_f32(x)), fptr(y), b, hi, wi, c, stream())
+    return y
+
+
+def pose(x, w, bias, nbins, num_kp, out, kp_value=None, kp_jacobian=None, fixed=(None, None, None)):
+    """HEEstimator's tail + keypoint_transformation: x NHWC [B,h,w,C], w [3 nbins + 3 + 3 K, C] (rows yaw, pitch, roll, t, exp),
+    out: dict of contiguous fp32 buffers raw [B,3 nbins + 3 + 3 K], degrees [B,3], rot [B,3,3], and with kp_value [1|B,K,3] value
+    [B,K,3], with kp_jacobian [1|B,K,3,3] jacobian [B,K,3,3].  fixed: (yaw, pitch, roll) degrees that replace the estimate, or None."""
+    b, h, ww, c = x.shape
+    nout = 3 * nbins + 3 + 3 * num_kp
+    if tuple(w.shape) != (nout, c) or bias.numel() != nout or not x.is_contiguous():
+        raise RuntimeError(f"pose: w [{nout},{c}], bias [{nout}], x contiguous NHWC")
+    p = lib.PoseParams()
+    p.x, p.w, p.bias = fptr(x), fptr(w), fptr(bias)
+    p.raw, p.degrees, p.rot = fptr(out["raw"]), fptr(out["degrees"]), fptr(out["rot"])
+    if out["raw"].numel() != b * nout or out["degrees"].numel() != b * 3 or out["rot"].numel() != b * 9:
+        raise RuntimeError("pose: raw / degrees / rot sizes")
+    if kp_value is not None:
+        if kp_value.shape[0] not in (1, b) or tuple(kp_value.shape[1:]) != (num_kp, 3) or out["value"].numel() != b * num_kp * 3:
+            raise RuntimeError("pose: kp_value [1|B,K,3] and value [B,K,3]")
+        p.kp_value, p.value, p.kp_batch = fptr(kp_value), fptr(out["value"]), kp_value.shape[0]
+        if kp_jacobian is not None:
+            if kp_jacobian.shape[0] != kp_value.shape[0] or kp_jacobian.numel() != kp_value.numel() * 3 or out["jacobian"].numel() != b * num_kp * 9:
+                raise RuntimeError("pose: kp_jacobian [1|B,K,3,3] and jacobian [B,K,3,3]")
+            p.kp_jacobian, p.jacobian = fptr(kp_jacobian), fptr(out["jacobian"])
+    elif kp_jacobian is not None:
+        raise RuntimeError("pose: kp_jacobian goes with kp_value")
+    p.B, p.HW, p.C, p.x_cstride, p.nbins, p.K = b, h * ww, c, c, int(nbins), int(num_kp)
+    mask = 0
+    for i, (name, v) in enumerate(zip(("yaw", "pitch", "roll"), fixed)):
+        if v is not None:
+            mask |= 1 << i
+            setattr(p, name, float(v))
+    p.fixed_mask = mask
+    call("e4s_pose_f32", ctypes.byref(p), stream())
+    return out
+
+
+def conv_smallcin_into(x, wp, bias, y, k, stride, pad, relu=False):
+    """e4s_conv_smallcin_f32 (a k x k conv of an image of <= 4 channels) into the caller's NHWC buffer y."""
+    b, hi, wi, cin = x.shape
+    ho, wo = (hi + 2 * pad - k) // stride + 1, (wi + 2 * pad - k) // stride + 1
+    if tuple(y.shape[:3]) != (b, ho, wo) or not y.is_contiguous() or not x.is_contiguous():
+        raise RuntimeError(f"conv_smallcin_into: y holds {(b, ho, wo)} pixels")
+    call("e4s_conv_smallcin_f32", fptr(x), fptr(wp), fptr(bias), fptr(y), b, hi, wi, cin, ho, wo, y.shape[3], k, stride, pad,
+         1 if relu else 0, stream())
+    return y

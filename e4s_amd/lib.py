@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E4S_LIB_PATH") or os.path.join(_HERE, "libe4s_hip.so")      # (E4S_LIB_PATH: A/B runs of two builds)
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -111,6 +111,27 @@ class RetinaGeom(ctypes.Structure):
         ("lh", c_i * 3), ("lw", c_i * 3), ("step", c_i * 3), ("base", c_i * 3),
         ("min_size", (c_f * 2) * 3),
         ("resize", c_f),
+    ]
+
+
+class Conv3dParams(ctypes.Structure):
+    """Mirror of ``e4s_conv3d_params`` (include/e4s_hip.h)."""
+    _fields_ = [
+        ("x", c_p), ("w", c_p), ("bias", c_p), ("y", c_p),
+        ("x_bstride", c_l), ("x_dstride", c_l), ("x_ystride", c_l), ("x_xstride", c_l),
+        ("B", c_i), ("D", c_i), ("Hi", c_i), ("Wi", c_i), ("Cin", c_i), ("Cout", c_i),
+        ("y_cstride", c_i),
+        ("up2", c_i), ("relu", c_i), ("precision", c_i),
+    ]
+
+
+class PoseParams(ctypes.Structure):
+    """Mirror of ``e4s_pose_params`` (include/e4s_hip.h)."""
+    _fields_ = [
+        ("x", c_p), ("w", c_p), ("bias", c_p), ("kp_value", c_p), ("kp_jacobian", c_p),
+        ("raw", c_p), ("degrees", c_p), ("rot", c_p), ("value", c_p), ("jacobian", c_p),
+        ("B", c_i), ("HW", c_i), ("C", c_i), ("x_cstride", c_i), ("nbins", c_i), ("K", c_i), ("kp_batch", c_i), ("fixed_mask", c_i),
+        ("yaw", c_f), ("pitch", c_f), ("roll", c_f),
     ]
 
 
@@ -285,11 +306,18 @@ SIGNATURES = {
     "e4s_retina_head_f32": [c_p, c_i, c_p, c_p, ctypes.POINTER(RetinaGeom), c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "e4s_retina_decode_f32": [c_p, c_p, c_p, ctypes.POINTER(RetinaGeom), c_i, c_p, c_p, c_p, c_p],
     "e4s_retina_select_f32": [c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_f, c_i, c_i, c_f, c_p, c_p, c_p, c_p],
+    "e4s_conv3d_f32": [ctypes.POINTER(Conv3dParams), c_p],
+    "e4s_conv3d_pack_f32": [c_p, c_p, c_i, c_i, c_i, c_p],
+    "e4s_conv3d_pack_bytes": [c_i, c_i],
+    "e4s_softargmax3d_f32": [c_p, c_l, c_l, c_l, c_p, c_l, c_l, c_l] + [c_i] * 6 + [c_f, c_p, c_p, c_p],
+    "e4s_aa_down_f32": [c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_p],
+    "e4s_avgpool2_f32": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
+    "e4s_pose_f32": [ctypes.POINTER(PoseParams), c_p],
 }
 
 INT64_RETURN = {"e4s_split16_bytes", "e4s_instnorm_ws_doubles", "e4s_conv_bwd_ws_floats", "e4s_grouped_linear_t_ws_floats", "e4s_reduce_parts_ws_floats", "e4s_instnorm_bwd_ws_doubles", "e4s_prelu_bwd_ws_floats", "e4s_conv_wgrad_ws_floats", "e4s_conv_bf16x3_ws_floats", "e4s_conv_region_ws_floats", "e4s_lpips_layer_ws_doubles", "e4s_conv_mfma_ws_floats",
                 "e4s_cosine_ws_doubles", "e4s_region_mean_ws_floats", "e4s_colsum_ws_floats", "e4s_scale_dot_ws_floats", "e4s_wino_weights_bytes", "e4s_conv_wino_ws_floats", "e4s_rrdb_pack_bytes", "e4s_pconv_pack_bytes", "e4s_rconv_pack_bytes",
-                "e4s_ranger_multi_ws_floats"}       # size queries: return a count, not an error code
+                "e4s_ranger_multi_ws_floats", "e4s_conv3d_pack_bytes"}       # size queries: return a count, not an error code
 
 _lib = None
 

@@ -387,3 +387,28 @@ def synth_retinaface_frame_u8(batch, h, w, seed=0):
     """Seeded uint8 BGR frames [batch,h,w,3] for the detector checks (synth_image cropped to h x w, mapped to 0..255)."""
     x = synth_image(batch, max(h, w), seed=seed, tag="retinaface.in")[:, :, :h, :w]
     return ((x + 1) * 127.5).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+def synth_vid2vid_state_dict(module, seed=0):
+    """Seeded weights of a face-vid2vid KPDetector or HEEstimator (the reference's or e4s_amd.reenact's: chosen by key and shape
+    only): synth_module_state_dict -- BatchNorm scale 1 +- 0.1 with running statistics near (0, 1), so folding them is not a no-op --
+    and, so that activations neither die nor blow up: every conv in front of a ReLU x sqrt(2), each ResBottleneck's norm3 scale x 0.5
+    (a block then adds about a quarter of its input's variance to the identity).  The keypoint head keeps the plain fan-in scale:
+    its logits of about +-0.7, divided by the temperature 0.1, give heat maps that are neither flat nor a single voxel, so the
+    soft-argmax is more than a mean and more than an argmax.  The anti-alias buffer `down.weight` keeps the module's own value."""
+    sd = synth_module_state_dict(module, seed=seed, tag="vid2vid.")
+    own = module.state_dict()
+    for k in sd:
+        if k == "down.weight":
+            sd[k] = own[k].detach().clone().float()
+        elif sd[k].dim() >= 4 and not k.startswith(("kp.", "jacobian.", "predictor.conv.")) and not k.endswith(("conv3.weight", "skip.weight")):
+            sd[k] = sd[k] * math.sqrt(2.0)
+        elif k.endswith(".norm3.weight"):                                       # a ResBottleneck's (the estimator's own is "norm3.weight")
+            sd[k] = sd[k] * 0.5
+    return sd
+
+
+def synth_vid2vid_frames(batch, h, w, seed=0):
+    """Seeded float32 frames [batch,h,w,3] in [0,1] for the re-enactment checks (synth_image cropped to h x w)."""
+    x = synth_image(batch, max(h, w), seed=seed, tag="vid2vid.in")[:, :, :h, :w]
+    return ((x + 1) * 0.5).clamp(0, 1).permute(0, 2, 3, 1).contiguous()

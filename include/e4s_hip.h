@@ -867,6 +867,67 @@ int e4s_retina_select_f32(const float* boxes, const float* landms, const float* 
                           int N, float conf_thr, float nms_thr, int top_k, int keep_top_k, float ss, float* dets, float* lm_out,
                           int* counts, void* stream);
 
+/* ---- face-vid2vid keypoints and head pose (ABI v22; e4s_amd/reenact.py, src/pretrained/face_vid2vid/; csrc/vid2vid.hip) ------- */
+/* Zero-padded 3x3x3 conv, stride 1, channels-last fp32, Cin a multiple of 32, any Cout, D, Hi and Wi.  x: the first Cin channels of
+ * voxel (b, d, y, x) at element offset b x_bstride + d x_dstride + y x_ystride + x x_xstride (each a multiple of 4; a contiguous
+ * NDHWC volume, or an NHWC map [B,h,w,D C] read as [B,D,h,w,C]).  up2 = 1: the conv runs on the nearest (1, 2, 2) up-sampling of x
+ * (grid position (d, gy, gx) reads (d, gy >> 1, gx >> 1)), which is never written.  y: the first Cout channels of the contiguous
+ * [B,D,Ho,Wo,y_cstride]; nothing else is written.  v = acc + bias[c] (bias [Cout] or NULL; eval BatchNorm3d folded on the host),
+ * ReLU with relu.  precision 0: split-bf16 (three bf16 MFMAs per product, fp32 accumulate); 1: exact fp32 MFMA.  The summation
+ * order of an output is (tap kd, ky, kx; 32-channel chunk; k-step), whatever the batch or the position.  w: packed by
+ * e4s_conv3d_pack_f32 for the same precision. */
+typedef struct {
+    const float* x;
+    const float* w;
+    const float* bias;
+    float* y;
+    int64_t x_bstride, x_dstride, x_ystride, x_xstride;
+    int B, D, Hi, Wi, Cin, Cout;
+    int y_cstride;
+    int up2, relu, precision;
+} e4s_conv3d_params;
+int e4s_conv3d_f32(const e4s_conv3d_params* p, void* stream);
+/* w [Cout][Cin][3][3][3] (nn.Conv3d) -> out [ceil(Cout/32)][27][Cin/32][32][128 bytes] (e4s_conv3d_pack_bytes bytes; 0 for sizes
+ * the kernel does not take; rows of channels past Cout are zero): 32 floats per row (split = 0, for precision 1) or [32 hi | 32
+ * lo] bf16 (split = 1) */
+int e4s_conv3d_pack_f32(const float* w, void* out, int Cin, int Cout, int split, void* stream);
+int64_t e4s_conv3d_pack_bytes(int Cin, int Cout);
+/* KPDetector's head: softmax of logit / temperature over the D H W voxels of keypoint k and the expectation of
+ * make_coordinate_grid (x, y, z; 2 i / (n - 1) - 1) -> value [B,K,3]; with jac the heat-map-weighted sum of jacobian maps
+ * (njmaps = K or 1; map j entry e is channel j * 9 + e) -> jacobian [B,K,9].  Element strides: logit (b, k, voxel v) at b l_bstride
+ * + k l_kstride + v l_vstride, jacobian channel c at b j_bstride + c j_cstride + v j_vstride (NCDHW or NDHWC alike).  Sums are
+ * taken in an order fixed by (D, H, W). */
+int e4s_softargmax3d_f32(const float* logits, int64_t l_bstride, int64_t l_kstride, int64_t l_vstride, const float* jac,
+                         int64_t j_bstride, int64_t j_cstride, int64_t j_vstride, int njmaps, int B, int K, int D, int H, int W,
+                         float temperature, float* value, float* jacobian, void* stream);
+/* AntiAliasInterpolation2d at the kept positions only: src [B,H,W,3] fp32 or uint8 (is_u8 = 1, read as x / 255) -> dst fp32
+ * [B,ceil(H/step),ceil(W/step),3]; dst(oy, ox) = sum_ky taps[ky] sum_kx taps[kx] src(oy step + ky - ntaps/2, ox step + kx -
+ * ntaps/2), taps outside the image are zero.  taps: ntaps (odd) DEVICE floats.  ntaps = 1, step = 1 converts a frame. */
+int e4s_aa_down_f32(const void* src, int is_u8, float* dst, int B, int H, int W, const float* taps, int ntaps, int step, void* stream);
+/* nn.AvgPool2d(2) on NHWC x [B,Hi,Wi,C] -> y [B,Hi/2,Wi/2,C] (odd sizes drop the last row / column); C % 4 == 0, Hi, Wi >= 2 */
+int e4s_avgpool2_f32(const float* x, float* y, int B, int Hi, int Wi, int C, void* stream);
+/* HEEstimator's tail and keypoint_transformation in one launch, one block per frame: the global average pool of x [B,HW,x_cstride]
+ * (C <= 2048 channels), the five linear heads as w [3 nbins + 3 + 3 K][C] + bias, rows in the order yaw (the reference's fc_roll),
+ * pitch, roll (its fc_yaw), t, exp -> raw [B,3 nbins + 3 + 3 K]; degrees [B,3] = softmax expectation * 3 - 99 per angle; angle i of
+ * fixed_mask bit i (yaw, pitch, roll) is replaced by the given constant; rot [B,9] = Rx(pitch) Ry(yaw) Rz(roll) with pi = 3.14.
+ * With kp_value [kp_batch,K,3] (kp_batch 1 or B): value [B,K,3] = rot kp + t + exp; with kp_jacobian [kp_batch,K,9]: jacobian
+ * [B,K,9] = rot J. */
+typedef struct {
+    const float* x;
+    const float* w;
+    const float* bias;
+    const float* kp_value;
+    const float* kp_jacobian;
+    float* raw;
+    float* degrees;
+    float* rot;
+    float* value;
+    float* jacobian;
+    int B, HW, C, x_cstride, nbins, K, kp_batch, fixed_mask;
+    float yaw, pitch, roll;
+} e4s_pose_params;
+int e4s_pose_f32(const e4s_pose_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
