@@ -769,6 +769,13 @@ def instnorm_apply(x, stats, gate=None, res=None, res_stats=None, slope=None, rs
     """want_stats: also return the InstanceNorm statistics of the OUTPUT ((y, stats [B,C,2])), accumulated by the same
     pass (the next encoder unit normalises this tensor first thing, helpers.py:128)."""
     b, h, w, c = x.shape
+    # the kernels index these by (b, c) and res as [B, H rs, W rs, C] without looking at their extents: a residual from an odd map
+    # (15^2 -> 8^2 at stride 2) would be read past its end
+    if res is not None and tuple(res.shape) != (b, h * rs, w * rs, c):
+        raise ValueError(f"instnorm_apply: res {tuple(res.shape)} is not [B, H rs, W rs, C] = {(b, h * rs, w * rs, c)} (rs = {rs})")
+    for name, t, n in (("stats", stats, b * c * 2), ("res_stats", res_stats, b * c * 2), ("gate", gate, b * c), ("slope", slope, c)):
+        if t is not None and t.numel() != n:
+            raise ValueError(f"instnorm_apply: {name} has {t.numel()} elements, expected {n}")
     y = torch.empty_like(x)
     if want_stats and c % 64 == 0:
         ws = torch.empty(lib.load().e4s_instnorm_ws_doubles(b, h * w, c), device=x.device, dtype=torch.float64)

@@ -1,6 +1,7 @@
 """A stand-in for `torch` inside e4s_amd.kernels that puts every tensor a wrapper allocates (outputs and workspaces) between two bands of
 a sentinel value, so that a write next to a tensor and an element left unwritten both show.  A plain helper module of the GPU kernel
-tests (tests/test_gpu_gen_backward_kernels.py, tests/test_gpu_encoder_backward_kernels.py); it holds no test."""
+tests (tests/test_gpu_gen_backward_kernels.py, tests/test_gpu_encoder_backward_kernels.py, tests/test_gpu_encoder_forward_kernels.py);
+it holds no test."""
 import torch
 
 DEV = "cuda"
