@@ -19,6 +19,15 @@
 // (tap kd-major then ky then kx, 32-channel chunk, k-step) whatever the batch, the voxel's position or the tile's place: a tap that
 // leaves the volume contributes exact zeros in its turn.
 //
+// The family (e4s_conv3dx_f32, ABI v23; the dense motion network and the ResBlock3d stack of reenact_warp.py) is the same tile code
+// with the kernel's edge KS = 1, 3 or 7 as a template parameter (KS = 3 is the kernel above, instruction for instruction) and a
+// residual read through its own strides in the epilogue (v = acc + bias + res, then the ReLU).  Channel-slice outputs are y advanced
+// to the slice with the buffer's y_cstride; Cin 80 and 112 are a padded channel stride whose pad channels hold zeros, with zero
+// weight columns; x_bstride = 0 broadcasts a batch-1 input.  KS = 7 (Cin 112 -> 16 on a 16-deep volume): a tile skips the kd planes
+// that leave the volume for all of its voxels; their steps would add exact zeros to accumulators that are never -0, so the order of
+// the in-range steps, and every bit, stays (test_new_convs_batch_and_position_do_not_change_the_bits).  Cout = 16 runs the BN = 32
+// tile with half of its columns idle.
+//
 // Soft-argmax head: one block per (sample, keypoint).  m = max logit / T; every thread adds exp(logit / T - m) times (1, x, y, z, the
 // nine jacobian maps) over voxels tid, tid + 256, ... in rising order, then a fixed binary tree over the 256 partials; value = sums /
 // sum.  The order depends on (D, H, W) only.
@@ -34,8 +43,10 @@ constexpr int BM = 128, NTHR = 256, YLD = 36;
 constexpr int A_BYTES = BM * ROWB;                                              // 16 384
 
 // F32: 1 = exact fp32 MFMA, 0 = split-bf16; BN: output channels per block (32, 64 or 128); UP2: the (1, 2, 2) nearest up-sampling
-template <int F32, int BN, int UP2>
-__global__ __launch_bounds__(NTHR) void conv3d_kernel(const e4s_conv3d_params p, const int Ho, const int Wo, const int M) {
+// KS: the kernel's edge (1, 3 or 7; padding KS / 2)
+template <int F32, int BN, int UP2, int KS>
+__global__ __launch_bounds__(NTHR) void conv3d_kernel(const e4s_conv3dx_params p, const int Ho, const int Wo, const int M) {
+    constexpr int PAD = KS / 2, NTAP = KS * KS * KS;
     constexpr int WN = BN >= 64 ? 2 : 1, WM = 4 / WN;           // waves along the channels / the voxels
     constexpr int TM = BM / (WM * 32), TN = BN / (WN * 32);     // 32 x 32 tiles per wave
     constexpr int BPIECES = BN * 8;                             // 16-byte weight pieces per step
@@ -55,7 +66,7 @@ __global__ __launch_bounds__(NTHR) void conv3d_kernel(const e4s_conv3d_params p,
     const int wm = wave % WM, wn = wave / WM;
     const int m0 = blockIdx.x * BM;
     const int nchunk = p.Cin / KC;
-    const int nstep = 27 * nchunk;
+    const int nstep = NTAP * nchunk;
     const int Hg = UP2 ? 2 * p.Hi : p.Hi, Wg = UP2 ? 2 * p.Wi : p.Wi;          // the grid the padding applies on (= Ho x Wo)
 
     // this thread's two gathered items: (voxel row m, 8-channel group q)
@@ -70,10 +81,10 @@ __global__ __launch_bounds__(NTHR) void conv3d_kernel(const e4s_conv3d_params p,
         const int mm = a_live[j] ? m : 0;
         const int ox = mm % Wo;
         int t = mm / Wo;
-        a_x[j] = ox - 1;
-        a_y[j] = t % Ho - 1;
+        a_x[j] = ox - PAD;
+        a_y[j] = t % Ho - PAD;
         t /= Ho;
-        a_d[j] = t % p.D - 1;
+        a_d[j] = t % p.D - PAD;
         a_base[j] = (int64_t)(t / p.D) * p.x_bstride + (item & 3) * 8;
     }
     const f32x8 zero8 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -82,7 +93,7 @@ __global__ __launch_bounds__(NTHR) void conv3d_kernel(const e4s_conv3d_params p,
     const unsigned char* wbase = reinterpret_cast<const unsigned char*>(p.w);
     auto fetch = [&](int step) {
         const int tap = step / nchunk, chunk = step - tap * nchunk;
-        const int kd = tap / 9, ky = (tap - kd * 9) / 3, kx = tap % 3;
+        const int kd = tap / (KS * KS), ky = (tap - kd * (KS * KS)) / KS, kx = tap % KS;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int id = a_d[j] + kd, gy = a_y[j] + ky, gx = a_x[j] + kx;
@@ -96,7 +107,7 @@ __global__ __launch_bounds__(NTHR) void conv3d_kernel(const e4s_conv3d_params p,
             const int i = tid + NTHR * j;
             const int row = i >> 3;
             const int cb32 = blockIdx.y * (BN / 32) + (row >> 5);
-            const unsigned char* wb = wbase + (((size_t)cb32 * 27 + tap) * nchunk + chunk) * (32 * ROWB) + (size_t)(row & 31) * ROWB + (i & 7) * 16;
+            const unsigned char* wb = wbase + (((size_t)cb32 * NTAP + tap) * nchunk + chunk) * (32 * ROWB) + (size_t)(row & 31) * ROWB + (i & 7) * 16;
             rb[j] = *reinterpret_cast<const f32x4*>(wb);
         }
     };
@@ -134,11 +145,23 @@ __global__ __launch_bounds__(NTHR) void conv3d_kernel(const e4s_conv3d_params p,
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
 
-    fetch(0);
-    for (int step = 0; step < nstep; ++step) {
+    // KS = 7: the kd planes that leave the volume for EVERY voxel of the tile are skipped.  Each of their steps would add exact zeros to
+    // accumulators that are never -0, so the in-range steps, still in rising order, give the same bits.
+    int step_lo = 0, step_hi = nstep;
+    if (KS == 7) {
+        const int per = Ho * Wo;
+        const int v0 = m0 / per, v1 = (m0 + BM - 1 < M ? m0 + BM - 1 : M - 1) / per;
+        const bool one = v0 / p.D == v1 / p.D;                 // the tile lies in one sample
+        const int dlo = one ? v0 % p.D : 0, dhi = one ? v1 % p.D : p.D - 1;
+        const int kd_lo = PAD - dhi > 0 ? PAD - dhi : 0, kd_hi = p.D - 1 + PAD - dlo < KS - 1 ? p.D - 1 + PAD - dlo : KS - 1;
+        step_lo = kd_lo * KS * KS * nchunk;
+        step_hi = (kd_hi + 1) * KS * KS * nchunk;
+    }
+    fetch(step_lo);
+    for (int step = step_lo; step < step_hi; ++step) {
         __syncthreads();                                        // every reader of the previous step's LDS image is done
         stage();
-        if (step + 1 < nstep) fetch(step + 1);
+        if (step + 1 < step_hi) fetch(step + 1);
         __syncthreads();
         if (F32) {
             // lane (li, kh) holds channels 4 (2 gp + kh) + s of its row, for A and B alike
@@ -204,6 +227,21 @@ __global__ __launch_bounds__(NTHR) void conv3d_kernel(const e4s_conv3d_params p,
                 const int c = co + c4 * 4;
                 if (pix < 0 || c >= p.Cout) continue;
                 f32x4 v = *reinterpret_cast<const f32x4*>(myY + row * YLD + c4 * 4);
+                if (p.res) {
+                    const int ox = pix % Wo;
+                    int t = pix / Wo;
+                    const int oy = t % Ho;
+                    t /= Ho;
+                    const float* rs = p.res + (int64_t)(t / p.D) * p.r_bstride + (int64_t)(t % p.D) * p.r_dstride + (int64_t)oy * p.r_ystride +
+                                      (int64_t)ox * p.r_xstride + c;
+                    if (vec) {
+                        v += *reinterpret_cast<const f32x4*>(rs);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (c + e < p.Cout) v[e] += rs[e];
+                    }
+                }
                 if (p.relu) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
@@ -220,9 +258,9 @@ __global__ __launch_bounds__(NTHR) void conv3d_kernel(const e4s_conv3d_params p,
         }
 }
 
-// w [Cout][Cin][3][3][3] (nn.Conv3d) -> [ceil(Cout / 32)][27][Cin / 32][32 co][128 bytes]; rows of channels past Cout are zero
+// w [Cout][Cin][ntap] (nn.Conv3d) -> [ceil(Cout / 32)][ntap][Cin / 32][32 co][128 bytes]; rows of channels past Cout are zero
 template <int SPLIT>
-__global__ void conv3d_pack_kernel(const float* __restrict__ w, unsigned char* __restrict__ out, int Cin, int Cout, int64_t n) {
+__global__ void conv3d_pack_kernel(const float* __restrict__ w, unsigned char* __restrict__ out, int Cin, int Cout, int ntap, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int ci = (int)(i & 31), co = (int)((i >> 5) & 31);
@@ -230,17 +268,19 @@ __global__ void conv3d_pack_kernel(const float* __restrict__ w, unsigned char* _
     const int nchunk = Cin / KC;
     const int chunk = (int)(rest % nchunk);
     rest /= nchunk;
-    const int tap = (int)(rest % 27);
-    const int c = (int)(rest / 27) * 32 + co;
-    const float v = c < Cout ? w[((size_t)c * Cin + chunk * KC + ci) * 27 + tap] : 0.f;
+    const int tap = (int)(rest % ntap);
+    const int c = (int)(rest / ntap) * 32 + co;
+    const float v = c < Cout ? w[((size_t)c * Cin + chunk * KC + ci) * ntap + tap] : 0.f;
     pack_row_store<SPLIT>(out + (size_t)(i >> 5) * ROWB, ci, v);
 }
 
 template <int F32, int BN>
-int launch_conv3d(const e4s_conv3d_params& p, int Ho, int Wo, int M, int cout_pad, hipStream_t st) {
+int launch_conv3d(const e4s_conv3dx_params& p, int Ho, int Wo, int M, int cout_pad, hipStream_t st) {
     const dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)(cout_pad / BN));
-    if (p.up2) hipLaunchKernelGGL((conv3d_kernel<F32, BN, 1>), grid, dim3(NTHR), 0, st, p, Ho, Wo, M);
-    else hipLaunchKernelGGL((conv3d_kernel<F32, BN, 0>), grid, dim3(NTHR), 0, st, p, Ho, Wo, M);
+    if (p.ksize == 7) hipLaunchKernelGGL((conv3d_kernel<F32, BN, 0, 7>), grid, dim3(NTHR), 0, st, p, Ho, Wo, M);
+    else if (p.ksize == 1) hipLaunchKernelGGL((conv3d_kernel<F32, BN, 0, 1>), grid, dim3(NTHR), 0, st, p, Ho, Wo, M);
+    else if (p.up2) hipLaunchKernelGGL((conv3d_kernel<F32, BN, 1, 3>), grid, dim3(NTHR), 0, st, p, Ho, Wo, M);
+    else hipLaunchKernelGGL((conv3d_kernel<F32, BN, 0, 3>), grid, dim3(NTHR), 0, st, p, Ho, Wo, M);
     E4S_CHECK_LAUNCH();
     return 0;
 }
@@ -337,7 +377,7 @@ __global__ __launch_bounds__(256) void aa_down_kernel(const void* __restrict__ s
 
 // ---- nn.AvgPool2d(2) on NHWC: Ho = Hi / 2, Wo = Wi / 2 (odd sizes drop their last row / column) ----
 __global__ __launch_bounds__(256) void avgpool2_kernel(const float* __restrict__ x, float* __restrict__ y, int Hi, int Wi, int Ho, int Wo,
-                                                       int C4, int64_t n) {
+                                                       int C4, int XS4, int YS4, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int c = (int)(i % C4);
@@ -346,9 +386,9 @@ __global__ __launch_bounds__(256) void avgpool2_kernel(const float* __restrict__
     t /= Wo;
     const int oy = (int)(t % Ho);
     const int64_t b = t / Ho;
-    const f32x4* src = reinterpret_cast<const f32x4*>(x) + ((b * Hi + 2 * oy) * Wi + 2 * ox) * C4 + c;
-    const f32x4 s = ((src[0] + src[C4]) + src[(int64_t)Wi * C4]) + src[(int64_t)Wi * C4 + C4];
-    reinterpret_cast<f32x4*>(y)[i] = s * 0.25f;
+    const f32x4* src = reinterpret_cast<const f32x4*>(x) + ((b * Hi + 2 * oy) * Wi + 2 * ox) * XS4 + c;
+    const f32x4 s = ((src[0] + src[XS4]) + src[(int64_t)Wi * XS4]) + src[(int64_t)Wi * XS4 + XS4];
+    reinterpret_cast<f32x4*>(y)[((b * Ho + oy) * Wo + ox) * YS4 + c] = s * 0.25f;
 }
 
 // ---- pose ----
@@ -443,30 +483,46 @@ __global__ __launch_bounds__(256) void pose_kernel(const e4s_pose_params p) {
 
 }  // namespace
 
-extern "C" int64_t e4s_conv3d_pack_bytes(int Cin, int Cout) {
-    return Cin >= KC && Cin % KC == 0 && Cout >= 1 ? (int64_t)((Cout + 31) / 32) * 27 * (Cin / KC) * 32 * ROWB : 0;
+static bool conv3d_ksize_ok(int k) { return k == 1 || k == 3 || k == 7; }
+
+extern "C" int64_t e4s_conv3dx_pack_bytes(int Cin, int Cout, int ksize) {
+    return conv3d_ksize_ok(ksize) && Cin >= KC && Cin % KC == 0 && Cout >= 1
+               ? (int64_t)((Cout + 31) / 32) * (ksize * ksize * ksize) * (Cin / KC) * 32 * ROWB
+               : 0;
 }
 
-extern "C" int e4s_conv3d_pack_f32(const float* w, void* out, int Cin, int Cout, int split, void* stream) {
-    const int64_t bytes = e4s_conv3d_pack_bytes(Cin, Cout);
+extern "C" int64_t e4s_conv3d_pack_bytes(int Cin, int Cout) { return e4s_conv3dx_pack_bytes(Cin, Cout, 3); }
+
+extern "C" int e4s_conv3dx_pack_f32(const float* w, void* out, int Cin, int Cout, int ksize, int split, void* stream) {
+    const int64_t bytes = e4s_conv3dx_pack_bytes(Cin, Cout, ksize);
     if (!w || !out || !aligned16(out) || bytes == 0) return (int)hipErrorInvalidValue;
     const int64_t n = bytes / ROWB * 32;
     if ((n + 255) / 256 >= (1ll << 31)) return (int)hipErrorInvalidValue;
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (split) hipLaunchKernelGGL(conv3d_pack_kernel<1>, grid, dim3(256), 0, as_stream(stream), w, static_cast<unsigned char*>(out), Cin, Cout, n);
-    else hipLaunchKernelGGL(conv3d_pack_kernel<0>, grid, dim3(256), 0, as_stream(stream), w, static_cast<unsigned char*>(out), Cin, Cout, n);
+    const int ntap = ksize * ksize * ksize;
+    if (split) hipLaunchKernelGGL(conv3d_pack_kernel<1>, grid, dim3(256), 0, as_stream(stream), w, static_cast<unsigned char*>(out), Cin, Cout, ntap, n);
+    else hipLaunchKernelGGL(conv3d_pack_kernel<0>, grid, dim3(256), 0, as_stream(stream), w, static_cast<unsigned char*>(out), Cin, Cout, ntap, n);
     E4S_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int e4s_conv3d_f32(const e4s_conv3d_params* pp, void* stream) {
-    const e4s_conv3d_params& p = *pp;
+extern "C" int e4s_conv3d_pack_f32(const float* w, void* out, int Cin, int Cout, int split, void* stream) {
+    return e4s_conv3dx_pack_f32(w, out, Cin, Cout, 3, split, stream);
+}
+
+extern "C" int e4s_conv3dx_f32(const e4s_conv3dx_params* pp, void* stream) {
+    const e4s_conv3dx_params& p = *pp;
     if (!p.x || !p.w || !p.y || p.B < 1 || p.D < 1 || p.Hi < 1 || p.Wi < 1) return (int)hipErrorInvalidValue;
     if (p.Cin < KC || p.Cin % KC || p.Cout < 1 || p.y_cstride < p.Cout) return (int)hipErrorInvalidValue;
     if ((p.up2 != 0 && p.up2 != 1) || (p.relu != 0 && p.relu != 1) || (p.precision != 0 && p.precision != 1)) return (int)hipErrorInvalidValue;
+    if (!conv3d_ksize_ok(p.ksize) || (p.up2 && p.ksize != 3)) return (int)hipErrorInvalidValue;
     if (p.x_bstride < 0 || p.x_dstride < 0 || p.x_ystride < 0 || p.x_xstride < p.Cin) return (int)hipErrorInvalidValue;
     if (p.x_bstride % 4 || p.x_dstride % 4 || p.x_ystride % 4 || p.x_xstride % 4) return (int)hipErrorInvalidValue;
     if (!aligned16(p.x) || !aligned16(p.w) || !aligned16(p.y)) return (int)hipErrorInvalidValue;
+    if (p.res) {
+        if (p.r_bstride < 0 || p.r_dstride < 0 || p.r_ystride < 0 || p.r_xstride < p.Cout) return (int)hipErrorInvalidValue;
+        if (p.r_bstride % 4 || p.r_dstride % 4 || p.r_ystride % 4 || p.r_xstride % 4 || !aligned16(p.res)) return (int)hipErrorInvalidValue;
+    }
     const int Ho = p.up2 ? 2 * p.Hi : p.Hi, Wo = p.up2 ? 2 * p.Wi : p.Wi;
     const int64_t M = (int64_t)p.B * p.D * Ho * Wo;
     if (M >= (1ll << 31) - BM) return (int)hipErrorInvalidValue;
@@ -478,6 +534,16 @@ extern "C" int e4s_conv3d_f32(const e4s_conv3d_params* pp, void* stream) {
     if (cout_pad % 64 == 0)
         return p.precision == 1 ? launch_conv3d<1, 64>(p, Ho, Wo, (int)M, cout_pad, st) : launch_conv3d<0, 64>(p, Ho, Wo, (int)M, cout_pad, st);
     return p.precision == 1 ? launch_conv3d<1, 32>(p, Ho, Wo, (int)M, cout_pad, st) : launch_conv3d<0, 32>(p, Ho, Wo, (int)M, cout_pad, st);
+}
+
+extern "C" int e4s_conv3d_f32(const e4s_conv3d_params* pp, void* stream) {
+    if (!pp) return (int)hipErrorInvalidValue;
+    e4s_conv3dx_params q = {};
+    q.x = pp->x, q.w = pp->w, q.bias = pp->bias, q.y = pp->y;
+    q.x_bstride = pp->x_bstride, q.x_dstride = pp->x_dstride, q.x_ystride = pp->x_ystride, q.x_xstride = pp->x_xstride;
+    q.B = pp->B, q.D = pp->D, q.Hi = pp->Hi, q.Wi = pp->Wi, q.Cin = pp->Cin, q.Cout = pp->Cout;
+    q.y_cstride = pp->y_cstride, q.ksize = 3, q.up2 = pp->up2, q.relu = pp->relu, q.precision = pp->precision;
+    return e4s_conv3dx_f32(&q, stream);
 }
 
 extern "C" int e4s_softargmax3d_f32(const float* logits, int64_t l_bstride, int64_t l_kstride, int64_t l_vstride, const float* jac,
@@ -504,14 +570,20 @@ extern "C" int e4s_aa_down_f32(const void* src, int is_u8, float* dst, int B, in
     return 0;
 }
 
-extern "C" int e4s_avgpool2_f32(const float* x, float* y, int B, int Hi, int Wi, int C, void* stream) {
+extern "C" int e4s_avgpool2s_f32(const float* x, float* y, int B, int Hi, int Wi, int C, int x_cstride, int y_cstride, void* stream) {
     if (!x || !y || B < 1 || Hi < 2 || Wi < 2 || C < 4 || C % 4 || !aligned16(x) || !aligned16(y)) return (int)hipErrorInvalidValue;
+    if (x_cstride < C || y_cstride < C || x_cstride % 4 || y_cstride % 4) return (int)hipErrorInvalidValue;
     const int Ho = Hi / 2, Wo = Wi / 2;
     const int64_t n = (int64_t)B * Ho * Wo * (C / 4);
     if ((n + 255) / 256 >= (1ll << 31)) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(avgpool2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), x, y, Hi, Wi, Ho, Wo, C / 4, n);
+    hipLaunchKernelGGL(avgpool2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), x, y, Hi, Wi, Ho, Wo, C / 4,
+                       x_cstride / 4, y_cstride / 4, n);
     E4S_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int e4s_avgpool2_f32(const float* x, float* y, int B, int Hi, int Wi, int C, void* stream) {
+    return e4s_avgpool2s_f32(x, y, B, Hi, Wi, C, C, C, stream);
 }
 
 extern "C" int e4s_pose_f32(const e4s_pose_params* pp, void* stream) {

@@ -2146,3 +2146,196 @@ def conv_smallcin_into(x, wp, bias, y, k, stride, pad, relu=False):
     call("e4s_conv_smallcin_f32", fptr(x), fptr(wp), fptr(bias), fptr(y), b, hi, wi, cin, ho, wo, y.shape[3], k, stride, pad,
          1 if relu else 0, stream())
     return y
+
+
+# ---- face-vid2vid dense motion and 3-D feature warp (reenact_warp.py) ---------------------------
+def _vol(t, what, c=None):
+    """Check an fp32 device volume [B,D,H,W,C] with contiguous channels (any other strides); c: the channels that are read."""
+    if t.dtype != torch.float32 or t.dim() != 5 or not t.is_cuda or t.stride(4) != 1 or (c is not None and t.shape[4] < c):
+        raise RuntimeError(f"{what}: an fp32 device volume [B,D,H,W,C] with contiguous channels" + (f" (C >= {c})" if c else ""))
+    return t
+
+
+def conv3dx_pack(w, f32, cin_pad=None):
+    """nn.Conv3d weight [Cout,Cin,k,k,k] (k 1, 3 or 7; any Cout) -> the opaque image e4s_conv3dx_f32 reads.  cin_pad: the input
+    channels are padded with zero columns to this multiple of 32 (Cin 80 -> 96, 112 -> 128: the conv then reads a buffer whose pad
+    channels hold zeros)."""
+    w = _f32(w)
+    if w.dim() != 5 or w.shape[2] != w.shape[3] or w.shape[2] != w.shape[4]:
+        raise RuntimeError(f"conv3dx_pack: a [Cout, Cin, k, k, k] weight, got {tuple(w.shape)}")
+    cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
+    cin_pad = cin if cin_pad is None else int(cin_pad)
+    if cin_pad < cin:
+        raise RuntimeError(f"conv3dx_pack: cin_pad {cin_pad} is below the weight's {cin} input channels")
+    if cin_pad != cin:
+        wide = torch.zeros(cout, cin_pad, k, k, k, device=w.device, dtype=torch.float32)
+        wide[:, :cin] = w
+        w = wide
+    nbytes = lib.load().e4s_conv3dx_pack_bytes(cin_pad, cout, k)
+    if nbytes == 0:
+        raise RuntimeError(f"conv3dx_pack: a [Cout, 32j, k, k, k] weight with k 1, 3 or 7 (after padding), got {tuple(w.shape)}")
+    out = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
+    call("e4s_conv3dx_pack_f32", fptr(w), ptr(out), cin_pad, cout, k, 0 if f32 else 1, stream())
+    out.conv3dx_f32 = bool(f32)
+    out.conv3dx_shape = (cout, cin_pad, k)
+    return out
+
+
+def conv3dx(x, w_pack, cout, y, *, y_coff=0, bias=None, res=None, relu=False, up2=False, f32=None):
+    """The 3-D conv family: the zero-padded k^3 conv of x fp32 [1|B,D,H,W,Cin] (contiguous channels, any other strides; a batch-1 x
+    is broadcast over y's batch) -> channels y_coff .. y_coff + cout of the contiguous y [B,D,Ho,Wo,C].  v = acc + bias + res, ReLU
+    with relu; res: a volume [B,D,Ho,Wo,>= cout] read through its strides.  up2 (k = 3): x is read through the nearest (1, 2, 2)
+    up-sampling.  Writes y in place and returns it."""
+    _vol(x, "conv3dx: x")
+    xb, d, hi, wi, cin = x.shape
+    ho, wo = (2 * hi, 2 * wi) if up2 else (hi, wi)
+    if y.dtype != torch.float32 or y.dim() != 5 or not y.is_contiguous() or tuple(y.shape[1:4]) != (d, ho, wo) or y.shape[4] < y_coff + cout \
+            or y_coff % 4 or y_coff < 0:
+        raise RuntimeError(f"conv3dx: y is a contiguous fp32 volume of {(d, ho, wo)} voxels with channels {y_coff} .. {y_coff + cout} (y_coff % 4 == 0), "
+                           f"got {tuple(y.shape)}")
+    b = y.shape[0]
+    if xb != b and xb != 1:
+        raise RuntimeError(f"conv3dx: x has batch {xb}, y {b}")
+    f32 = sr_f32() if f32 is None else bool(f32)
+    shape = getattr(w_pack, "conv3dx_shape", None)
+    if shape is None or shape[:2] != (cout, cin) or getattr(w_pack, "conv3dx_f32", None) != f32:
+        raise RuntimeError(f"conv3dx: w_pack is not conv3dx_pack's image of a [{cout},{cin},k,k,k] weight in this precision")
+    for name, t in (("w_pack", w_pack), ("y", y), ("bias", bias), ("res", res)):
+        if t is not None and t.device != x.device:
+            raise RuntimeError(f"conv3dx: {name} is on {t.device}, x on {x.device}")
+    p = lib.Conv3dxParams()
+    p.x, p.w, p.y = c_p(x.data_ptr()), fptr(w_pack), c_p(y.data_ptr() + 4 * y_coff)
+    if bias is not None:
+        if bias.numel() != cout:
+            raise RuntimeError(f"conv3dx: bias has {bias.numel()} entries for {cout} channels")
+        p.bias = fptr(_f32(bias))
+    if res is not None:
+        _vol(res, "conv3dx: res", cout)
+        if tuple(res.shape[:4]) != (b, d, ho, wo):
+            raise RuntimeError(f"conv3dx: res holds {tuple(res.shape[:4])} voxels, y {(b, d, ho, wo)}")
+        p.res = c_p(res.data_ptr())
+        p.r_bstride, p.r_dstride, p.r_ystride, p.r_xstride = res.stride(0), res.stride(1), res.stride(2), res.stride(3)
+    p.x_bstride, p.x_dstride, p.x_ystride, p.x_xstride = (x.stride(0) if xb == b else 0), x.stride(1), x.stride(2), x.stride(3)
+    p.B, p.D, p.Hi, p.Wi, p.Cin, p.Cout = b, d, hi, wi, cin, cout
+    p.y_cstride, p.ksize = y.shape[4], shape[2]
+    p.up2, p.relu, p.precision = 1 if up2 else 0, 1 if relu else 0, 1 if f32 else 0
+    call("e4s_conv3dx_f32", ctypes.byref(p), stream())
+    return y
+
+
+def avgpool2_into(x, c, y, y_coff=0):
+    """nn.AvgPool2d(2) of the first c channels of the contiguous NHWC x into channels y_coff .. y_coff + c of the contiguous NHWC y
+    [B,H/2,W/2,C] (AvgPool3d((1, 2, 2)) of a volume: its B D planes as the batch)."""
+    b, hi, wi, xc = x.shape
+    if x.dtype != torch.float32 or y.dtype != torch.float32 or not x.is_contiguous() or not y.is_contiguous() or xc < c \
+            or tuple(y.shape[:3]) != (b, hi // 2, wi // 2) or y.shape[3] < y_coff + c or y_coff % 4 or y_coff < 0 or not x.is_cuda or not y.is_cuda:
+        raise RuntimeError(f"avgpool2_into: contiguous fp32 NHWC device maps, y {(b, hi // 2, wi // 2)} pixels with channels {y_coff} .. {y_coff + c}")
+    call("e4s_avgpool2s_f32", c_p(x.data_ptr()), c_p(y.data_ptr() + 4 * y_coff), b, hi, wi, c, xc, y.shape[3], stream())
+    return y
+
+
+def bnrelu3d(x, scale, shift, y):
+    """y = relu(x * scale[c] + shift[c]): x a volume read through its strides, y the contiguous volume of its shape."""
+    _vol(x, "bnrelu3d: x")
+    b, d, h, w, c = x.shape
+    if tuple(y.shape) != tuple(x.shape) or not y.is_contiguous() or y.dtype != torch.float32 or scale.numel() != c or shift.numel() != c:
+        raise RuntimeError("bnrelu3d: y is the contiguous fp32 volume of x's shape; scale and shift have one entry per channel")
+    call("e4s_bnrelu3d_f32", c_p(x.data_ptr()), x.stride(0), x.stride(1), x.stride(2), x.stride(3), fptr(_f32(scale)), fptr(_f32(shift)),
+         fptr(y), b, d, h, w, c, stream())
+    return y
+
+
+def _kp(kp_source, kp_driving, jac, what):
+    n, k = kp_driving.shape[:2]
+    if tuple(kp_driving.shape) != (n, k, 3) or kp_source.shape[0] not in (1, n) or tuple(kp_source.shape[1:]) != (k, 3):
+        raise RuntimeError(f"{what}: kp_driving [N,K,3] and kp_source [1|N,K,3]")
+    if jac is not None and jac.numel() != n * k * 9:
+        raise RuntimeError(f"{what}: jac holds [N,K,3,3]")
+    return n, k
+
+
+def kp_jacobian(j_source, j_driving, out=None):
+    """J_source [1|N,K,3,3] @ inverse(J_driving [N,K,3,3]) -> [N,K,3,3] (the 3x3 inverse by cofactors)."""
+    n, k = j_driving.shape[:2]
+    if tuple(j_driving.shape) != (n, k, 3, 3) or j_source.shape[0] not in (1, n) or tuple(j_source.shape[1:]) != (k, 3, 3):
+        raise RuntimeError("kp_jacobian: j_driving [N,K,3,3] and j_source [1|N,K,3,3]")
+    out = torch.empty(n, k, 3, 3, device=j_driving.device, dtype=torch.float32) if out is None else out
+    call("e4s_kp_jacobian_f32", fptr(_f32(j_source)), j_source.shape[0], fptr(_f32(j_driving)), fptr(out), n, k, stream())
+    return out
+
+
+def sparse_warp(feat, kp_source, kp_driving, jac, y, y_coff=0, variance=0.01):
+    """DenseMotionNetwork's hourglass input.  feat: the compressed volume [1|N,D,H,W,4] (contiguous); kp_source [1|N,K,3], kp_driving
+    [N,K,3]; jac: kp_jacobian's [N,K,3,3] or None -> channels y_coff + 5 g .. + 4 (g = 0 .. K) of the contiguous y [N,D,H,W,C] = [the
+    heat-map difference of keypoint g - 1 (0 for g = 0), feat sampled under sparse motion g]."""
+    n, k = _kp(kp_source, kp_driving, jac, "sparse_warp")
+    fb, d, h, w, c = feat.shape
+    if c != 4 or not feat.is_contiguous() or feat.dtype != torch.float32 or fb not in (1, n):
+        raise RuntimeError(f"sparse_warp: feat is a contiguous fp32 volume [1|N,D,H,W,4], got {tuple(feat.shape)}")
+    if y.dtype != torch.float32 or not y.is_contiguous() or tuple(y.shape[:4]) != (n, d, h, w) or y.shape[4] < y_coff + 5 * (k + 1) or y_coff < 0:
+        raise RuntimeError(f"sparse_warp: y is a contiguous fp32 volume {(n, d, h, w)} with {5 * (k + 1)} channels from {y_coff}")
+    call("e4s_sparse_warp_f32", fptr(feat), fb, fptr(_f32(kp_source)), kp_source.shape[0], fptr(_f32(kp_driving)),
+         fptr(_f32(jac)) if jac is not None else None, c_p(y.data_ptr() + 4 * y_coff), y.shape[4], n, k, d, h, w, c, float(variance), stream())
+    return y
+
+
+def motion_combine(logits, kp_source, kp_driving, jac, mask=None, deformation=None):
+    """logits: the first K + 1 channels of a contiguous volume [N,D,H,W,C] -> (mask [N,D,H,W,K + 1] = their softmax, deformation
+    [N,D,H,W,3] = sum_g mask_g * sparse motion g).  The sparse motions are recomputed from the keypoints."""
+    n, k = _kp(kp_source, kp_driving, jac, "motion_combine")
+    if logits.dtype != torch.float32 or logits.dim() != 5 or not logits.is_contiguous() or logits.shape[0] != n or logits.shape[4] < k + 1:
+        raise RuntimeError(f"motion_combine: logits is a contiguous fp32 volume [N,D,H,W,>= {k + 1}]")
+    _, d, h, w, cs = logits.shape
+    mask = torch.empty(n, d, h, w, k + 1, device=logits.device, dtype=torch.float32) if mask is None else mask
+    deformation = torch.empty(n, d, h, w, 3, device=logits.device, dtype=torch.float32) if deformation is None else deformation
+    if tuple(mask.shape) != (n, d, h, w, k + 1) or tuple(deformation.shape) != (n, d, h, w, 3):
+        raise RuntimeError("motion_combine: mask [N,D,H,W,K + 1] and deformation [N,D,H,W,3]")
+    call("e4s_motion_combine_f32", fptr(logits), cs, fptr(_f32(kp_source)), kp_source.shape[0], fptr(_f32(kp_driving)),
+         fptr(_f32(jac)) if jac is not None else None, fptr(mask), fptr(deformation), n, k, d, h, w, stream())
+    return mask, deformation
+
+
+def warp3d(vol, deformation, y=None):
+    """F.grid_sample (trilinear, zero padding, align_corners False) of the ONE volume vol [1,D,H,W,C] (read through its strides)
+    under deformation [N,D,H,W,3] -> y NHWC [N,H,W,D * C] with channel d * C + c."""
+    _vol(vol, "warp3d: vol")
+    one, d, h, w, c = vol.shape
+    n = deformation.shape[0]
+    if one != 1 or tuple(deformation.shape) != (n, d, h, w, 3) or deformation.dtype != torch.float32:
+        raise RuntimeError(f"warp3d: a batch-1 volume and a deformation [N,{d},{h},{w},3] of its (d, h, w), got {tuple(vol.shape)} and {tuple(deformation.shape)}")
+    y = torch.empty(n, h, w, d * c, device=vol.device, dtype=torch.float32) if y is None else y
+    if tuple(y.shape) != (n, h, w, d * c) or not y.is_contiguous() or y.dtype != torch.float32:
+        raise RuntimeError(f"warp3d: y is a contiguous fp32 map {(n, h, w, d * c)}")
+    call("e4s_warp3d_f32", c_p(vol.data_ptr()), vol.stride(1), vol.stride(2), vol.stride(3), fptr(deformation), fptr(y), n, d, h, w, c, stream())
+    return y
+
+
+def occlusion_pack(w, depth):
+    """DenseMotionNetwork.occlusion's weight [1,C * depth,k,k] (input channel c * depth + d) -> [k,k,depth,C], e4s_occlusion_f32's."""
+    one, cd, k, k2 = w.shape
+    if one != 1 or k != k2 or cd % depth:
+        raise RuntimeError(f"occlusion_pack: a [1, C * {depth}, k, k] weight, got {tuple(w.shape)}")
+    return _f32(w).view(cd // depth, depth, k, k).permute(2, 3, 1, 0).contiguous()
+
+
+def occlusion(x, c, w_pack, bias, out=None):
+    """sigmoid(Conv2d(D * c -> 1, k x k, padding k / 2)) of the first c channels of the contiguous volume x [N,D,H,W,C] seen as the
+    map [N,c * D,H,W] -> [N,H,W]; w_pack: occlusion_pack's."""
+    n, d, h, w, cs = x.shape
+    k = w_pack.shape[0]
+    if x.dtype != torch.float32 or not x.is_contiguous() or cs < c or tuple(w_pack.shape) != (k, k, d, c) or not w_pack.is_contiguous():
+        raise RuntimeError(f"occlusion: x a contiguous fp32 volume with {c} or more channels, w_pack [k,k,{d},{c}]")
+    out = torch.empty(n, h, w, device=x.device, dtype=torch.float32) if out is None else out
+    if tuple(out.shape) != (n, h, w) or not out.is_contiguous():
+        raise RuntimeError(f"occlusion: out is a contiguous fp32 map {(n, h, w)}")
+    call("e4s_occlusion_f32", fptr(x), cs, fptr(w_pack), fptr(_f32(bias)) if bias is not None else None, fptr(out), n, d, h, w, c, k, stream())
+    return out
+
+
+def scale_rows(y, m):
+    """y [..., C] *= m [...] in place (the occlusion product): both contiguous fp32, C % 4 == 0."""
+    c = y.shape[-1]
+    if y.dtype != torch.float32 or not y.is_contiguous() or m.numel() * c != y.numel():
+        raise RuntimeError("scale_rows: y [..., C] contiguous fp32 and one multiplier per row")
+    call("e4s_scale_rows_f32", fptr(y), fptr(_f32(m)), y.numel() // c, c, stream())
+    return y

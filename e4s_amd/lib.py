@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E4S_LIB_PATH") or os.path.join(_HERE, "libe4s_hip.so")      # (E4S_LIB_PATH: A/B runs of two builds)
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -121,6 +121,19 @@ class Conv3dParams(ctypes.Structure):
         ("x_bstride", c_l), ("x_dstride", c_l), ("x_ystride", c_l), ("x_xstride", c_l),
         ("B", c_i), ("D", c_i), ("Hi", c_i), ("Wi", c_i), ("Cin", c_i), ("Cout", c_i),
         ("y_cstride", c_i),
+        ("up2", c_i), ("relu", c_i), ("precision", c_i),
+    ]
+
+
+class Conv3dxParams(ctypes.Structure):
+    """Mirror of ``e4s_conv3dx_params`` (include/e4s_hip.h)."""
+    _fields_ = [
+        ("x", c_p), ("w", c_p), ("bias", c_p), ("res", c_p), ("y", c_p),
+        ("x_bstride", c_l), ("x_dstride", c_l), ("x_ystride", c_l), ("x_xstride", c_l),
+        ("r_bstride", c_l), ("r_dstride", c_l), ("r_ystride", c_l), ("r_xstride", c_l),
+        ("B", c_i), ("D", c_i), ("Hi", c_i), ("Wi", c_i), ("Cin", c_i), ("Cout", c_i),
+        ("y_cstride", c_i),
+        ("ksize", c_i),
         ("up2", c_i), ("relu", c_i), ("precision", c_i),
     ]
 
@@ -313,11 +326,22 @@ SIGNATURES = {
     "e4s_aa_down_f32": [c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_p],
     "e4s_avgpool2_f32": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
     "e4s_pose_f32": [ctypes.POINTER(PoseParams), c_p],
+    "e4s_conv3dx_f32": [ctypes.POINTER(Conv3dxParams), c_p],
+    "e4s_conv3dx_pack_f32": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
+    "e4s_conv3dx_pack_bytes": [c_i, c_i, c_i],
+    "e4s_avgpool2s_f32": [c_p, c_p] + [c_i] * 6 + [c_p],
+    "e4s_bnrelu3d_f32": [c_p, c_l, c_l, c_l, c_l, c_p, c_p, c_p] + [c_i] * 5 + [c_p],
+    "e4s_kp_jacobian_f32": [c_p, c_i, c_p, c_p, c_i, c_i, c_p],
+    "e4s_sparse_warp_f32": [c_p, c_i, c_p, c_i, c_p, c_p, c_p] + [c_i] * 7 + [c_f, c_p],
+    "e4s_motion_combine_f32": [c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p] + [c_i] * 5 + [c_p],
+    "e4s_warp3d_f32": [c_p, c_l, c_l, c_l, c_p, c_p] + [c_i] * 5 + [c_p],
+    "e4s_occlusion_f32": [c_p, c_i, c_p, c_p, c_p] + [c_i] * 6 + [c_p],
+    "e4s_scale_rows_f32": [c_p, c_p, c_l, c_i, c_p],
 }
 
 INT64_RETURN = {"e4s_split16_bytes", "e4s_instnorm_ws_doubles", "e4s_conv_bwd_ws_floats", "e4s_grouped_linear_t_ws_floats", "e4s_reduce_parts_ws_floats", "e4s_instnorm_bwd_ws_doubles", "e4s_prelu_bwd_ws_floats", "e4s_conv_wgrad_ws_floats", "e4s_conv_bf16x3_ws_floats", "e4s_conv_region_ws_floats", "e4s_lpips_layer_ws_doubles", "e4s_conv_mfma_ws_floats",
                 "e4s_cosine_ws_doubles", "e4s_region_mean_ws_floats", "e4s_colsum_ws_floats", "e4s_scale_dot_ws_floats", "e4s_wino_weights_bytes", "e4s_conv_wino_ws_floats", "e4s_rrdb_pack_bytes", "e4s_pconv_pack_bytes", "e4s_rconv_pack_bytes",
-                "e4s_ranger_multi_ws_floats", "e4s_conv3d_pack_bytes"}       # size queries: return a count, not an error code
+                "e4s_ranger_multi_ws_floats", "e4s_conv3d_pack_bytes", "e4s_conv3dx_pack_bytes"}       # size queries: return a count, not an error code
 
 _lib = None
 

@@ -1,9 +1,9 @@
 """face-vid2vid's keypoint detector and head-pose estimator (src/pretrained/face_vid2vid/) -- MI355X-native.  Frames -> canonical
 keypoints, head pose in degrees, and the transformed keypoints `make_animation` (driven_demo.py:182-211) hands to its generator.
 
-This is everything `make_animation` computes before it calls the generator; the generator itself (dense motion, the 3-D warp, the
-SPADE decoder) is not provided.  `KPDetector` and `HEEstimator` take the reference's constructor arguments and hold the reference's
-parameter tree (modules/keypoint_detector.py, modules/util.py), so a checkpoint's ['kp_detector'] and ['he_estimator'] load with
+This is everything `make_animation` computes before it calls the generator; the generator's dense motion and 3-D feature warp are
+reenact_warp.py, its SPADE decoder is not provided.  `KPDetector` and `HEEstimator` take the reference's constructor arguments and
+hold the reference's parameter tree (modules/keypoint_detector.py, modules/util.py), so a checkpoint's ['kp_detector'] and ['he_estimator'] load with
 load_state_dict(strict=True).  The modules hold parameters only; execution is on channels-last buffers:
 
     reference                                               here

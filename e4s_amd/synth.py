@@ -412,3 +412,46 @@ def synth_vid2vid_frames(batch, h, w, seed=0):
     """Seeded float32 frames [batch,h,w,3] in [0,1] for the re-enactment checks (synth_image cropped to h x w)."""
     x = synth_image(batch, max(h, w), seed=seed, tag="vid2vid.in")[:, :, :h, :w]
     return ((x + 1) * 0.5).clamp(0, 1).permute(0, 2, 3, 1).contiguous()
+
+
+def synth_vid2vid_generator_state_dict(module, seed=0):
+    """Seeded weights of a face-vid2vid OcclusionAwareSPADEGenerator or DenseMotionNetwork (the reference's, or e4s_amd.reenact_warp's
+    FeatureWarp / DenseMotionNetwork: chosen by key and shape only, so the common keys get identical tensors and the reference's
+    `decoder.*` entries are simply more of them): synth_module_state_dict -- BatchNorm scale 1 +- 0.1 with running statistics near (0,
+    1), so folding them is not a no-op -- and, so that activations neither die nor blow up: every conv in front of a ReLU x sqrt(2);
+    each ResBlock3d's conv2 x 0.5 (a block adds about a quarter of its input's variance to the identity).  The heads keep the plain
+    fan-in scale except `mask`, x 2.5: its logits of a few units give a softmax over the 16 sparse motions that is neither flat nor
+    one-hot; `occlusion` has its mean removed (its inputs follow a ReLU, so a weight mean would push every pixel the same way) and
+    is x 4, and its bias + 1.5 (the channels' different means still leave the sum below zero), which spreads the sigmoid over most
+    of (0, 1)."""
+    sd = synth_module_state_dict(module, seed=seed, tag="vid2vid.gen.")
+    plain = ("second.weight", "fourth.weight", "mask.weight", "occlusion.weight")
+    for k in sd:
+        if k.startswith("decoder.") or sd[k].dim() < 4:
+            continue
+        if k.endswith("mask.weight"):
+            sd[k] = sd[k] * 2.5
+        elif k.endswith("occlusion.weight"):
+            sd[k] = (sd[k] - sd[k].mean()) * 4.0
+        elif ".3dr" in k and k.endswith("conv2.weight"):
+            sd[k] = sd[k] * 0.5
+        elif not k.endswith(plain):
+            sd[k] = sd[k] * math.sqrt(2.0)
+    for k in sd:
+        if k.endswith("occlusion.bias"):
+            sd[k] = sd[k] + 1.5
+    return sd
+
+
+def synth_vid2vid_keypoints(n, seed=0, jacobian=False):
+    """Seeded (kp_source, kp_driving) dicts for the dense-motion checks: one source set with values uniform in [-0.8, 0.8], n driving
+    sets = source + 0.15 randn; with jacobian, 'jacobian' = identity + 0.2 randn ([1,15,3,3] and [n,15,3,3]), else None.  float32."""
+    g = _gen("vid2vid.kp", seed)
+    sv = torch.rand(1, 15, 3, generator=g, dtype=torch.float32) * 1.6 - 0.8
+    dv = sv + 0.15 * torch.randn(n, 15, 3, generator=g, dtype=torch.float32)
+    sj = dj = None
+    if jacobian:
+        eye = torch.eye(3).view(1, 1, 3, 3)
+        sj = eye + 0.2 * torch.randn(1, 15, 3, 3, generator=g, dtype=torch.float32)
+        dj = eye + 0.2 * torch.randn(n, 15, 3, 3, generator=g, dtype=torch.float32)
+    return {"value": sv, "jacobian": sj}, {"value": dv, "jacobian": dj}

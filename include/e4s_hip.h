@@ -928,6 +928,65 @@ typedef struct {
 } e4s_pose_params;
 int e4s_pose_f32(const e4s_pose_params* p, void* stream);
 
+/* ---- face-vid2vid dense motion and 3-D feature warp (ABI v23; e4s_amd/reenact_warp.py; csrc/vid2vid.hip, csrc/vid2vid_warp.hip) ---- */
+/* The 3-D conv family.  e4s_conv3d_f32 with: ksize 1, 3 or 7 (a cube, zero padding ksize / 2; up2 needs ksize 3); res, an optional
+ * residual read at voxel (b, d, y, x) of the OUTPUT grid through its own element strides (each a multiple of 4, r_xstride >= Cout)
+ * and added before the ReLU: v = acc + bias[c] + res.  Channel counts that are no multiple of 32 (80, 112) run through a buffer
+ * whose channel stride is padded to one: Cin is the padded count, the pad channels of x hold zeros and the weight is packed with
+ * zero columns for them.  A channel-slice output is y advanced to the slice's first channel (a multiple of 4) with the buffer's
+ * y_cstride: an up block and its skip's producer write straight into the concat buffer.  x_bstride = 0 broadcasts a batch-1 input.
+ * Summation order of an output: (tap kd, ky, kx; 32-channel chunk; k-step), whatever the batch, the position or the tile; with
+ * ksize 7 a tile skips the kd planes that leave the volume for all of its voxels -- steps that would add exact zeros -- which
+ * changes no bit.  Every zero field reproduces e4s_conv3d_f32, which is this call with ksize 3 and no residual. */
+typedef struct {
+    const float* x;
+    const float* w;
+    const float* bias;
+    const float* res;
+    float* y;
+    int64_t x_bstride, x_dstride, x_ystride, x_xstride;
+    int64_t r_bstride, r_dstride, r_ystride, r_xstride;
+    int B, D, Hi, Wi, Cin, Cout;
+    int y_cstride;
+    int ksize;
+    int up2, relu, precision;
+} e4s_conv3dx_params;
+int e4s_conv3dx_f32(const e4s_conv3dx_params* p, void* stream);
+/* w [Cout][Cin][k][k][k] -> out [ceil(Cout/32)][k^3][Cin/32][32][128 bytes]; ksize 3 is e4s_conv3d_pack_f32 */
+int e4s_conv3dx_pack_f32(const float* w, void* out, int Cin, int Cout, int ksize, int split, void* stream);
+int64_t e4s_conv3dx_pack_bytes(int Cin, int Cout, int ksize);
+/* e4s_avgpool2_f32 with channel strides: the first C channels of x [B,Hi,Wi,x_cstride] -> the first C channels of y
+ * [B,Hi/2,Wi/2,y_cstride] (strides multiples of 4).  AvgPool3d((1, 2, 2)) of a volume is this over its B D planes. */
+int e4s_avgpool2s_f32(const float* x, float* y, int B, int Hi, int Wi, int C, int x_cstride, int y_cstride, void* stream);
+/* y = relu(x * scale[c] + shift[c]) (eval BatchNorm3d + ReLU; ResBlock3d's norm1, which sits in front of a zero-padded conv and so
+ * cannot be folded into it): x through element strides as in the conv, y contiguous [B,D,H,W,C], C % 4 == 0 */
+int e4s_bnrelu3d_f32(const float* x, int64_t x_bstride, int64_t x_dstride, int64_t x_ystride, int64_t x_xstride, const float* scale,
+                     const float* shift, float* y, int B, int D, int H, int W, int C, void* stream);
+/* out [N,K,9] = j_source [source_batch,K,9] (source_batch 1 or N) times the inverse of j_driving [N,K,9], row-major 3x3, by
+ * cofactors */
+int e4s_kp_jacobian_f32(const float* j_source, int source_batch, const float* j_driving, float* out, int N, int K, void* stream);
+/* The hourglass input of DenseMotionNetwork.  feat: the compressed volume [feat_batch,D,H,W,4] (feat_batch 1 or N; C must be 4);
+ * kp_source [kp_batch,K,3] (1 or N), kp_driving [N,K,3]; jac: e4s_kp_jacobian_f32's [N,K,9] or NULL.  Sparse motion 0 is
+ * make_coordinate_grid (x, y, z; 2 i / (n - 1) - 1), motion k + 1 is jac_k (grid - kp_driving_k) + kp_source_k.  Channels 5 g .. 5 g
+ * + 4 of y [N,D,H,W,y_cstride] (g = 0 .. K) = [exp(-|grid - kp_driving_k|^2 / (2 variance)) - the same with kp_source (0 for g =
+ * 0), the four features sampled under motion g: trilinear, zero padding, align_corners false].  K + 1 <= 32. */
+int e4s_sparse_warp_f32(const float* feat, int feat_batch, const float* kp_source, int kp_batch, const float* kp_driving,
+                        const float* jac, float* y, int y_cstride, int N, int K, int D, int H, int W, int C, float variance, void* stream);
+/* logits: the first K + 1 channels of [N,D,H,W,l_cstride] -> mask [N,D,H,W,K + 1] = their softmax, deformation [N,D,H,W,3] =
+ * sum_g mask_g * sparse motion g (recomputed from the keypoints as above), g in rising order */
+int e4s_motion_combine_f32(const float* logits, int l_cstride, const float* kp_source, int kp_batch, const float* kp_driving,
+                           const float* jac, float* mask, float* deformation, int N, int K, int D, int H, int W, void* stream);
+/* y [N,H,W,D C] (channel d C + c) = the trilinear sample (zero padding, align_corners false) of the ONE volume vol -- voxel (d, y, x)
+ * at d v_dstride + y v_ystride + x v_xstride, C % 4 == 0 contiguous channels -- under deformation [N,D,H,W,3] (x, y, z) */
+int e4s_warp3d_f32(const float* vol, int64_t v_dstride, int64_t v_ystride, int64_t v_xstride, const float* deformation, float* y, int N,
+                   int D, int H, int W, int C, void* stream);
+/* out [N,H,W] = sigmoid(bias[0] + the zero-padded ksize x ksize conv to one channel of x [N,D,H,W,x_cstride] seen as a map of D C
+ * channels); w [ksize][ksize][D][C], C % 4 == 0.  A reduction, one block per output pixel, in an order fixed by (ksize, D, C). */
+int e4s_occlusion_f32(const float* x, int x_cstride, const float* w, const float* bias, float* out, int N, int D, int H, int W, int C,
+                      int ksize, void* stream);
+/* y [rows,C] *= m [rows], in place; C % 4 == 0 */
+int e4s_scale_rows_f32(float* y, const float* m, int64_t rows, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
