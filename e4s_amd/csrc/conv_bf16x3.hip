@@ -25,6 +25,7 @@
 // The 144-byte row stride makes the ds_read_b128 fragment reads (lane -> row, lane half -> +16 B) conflict free, the
 // same argument as conv_mfma.hip.
 #include "common.h"
+#include "few_tile_geom.h"
 #include <stdlib.h>
 
 namespace {
@@ -108,7 +109,24 @@ inline void few_tiles_split(int64_t tiles, int nchunk, int& ksplit, int& cper) {
     ksplit = (nchunk + cper - 1) / cper;
 }
 
+// E4S_REGION_PACK=0: small masked maps keep one image per tile (the A/B switch of the packed tiles; read once, like E4S_REGION_1W)
+inline bool region_pack_mode() {
+    static const bool m = [] { const char* e = getenv("E4S_REGION_PACK"); return e ? atoi(e) != 0 : true; }();
+    return m;
+}
+
+// masked launches on maps small enough that a 256-row tile holds several whole images (few_tile_geom.h): by map shape only
+inline bool region_packed(const e4s_conv_params& p) {
+    return region_pack_mode() && p.labels && (p.ncls == 1 || p.ncls == 4) && e4s_few_tile::pack_geom(p.Ha, p.Wa).n_img >= 2;
+}
+
+// the ONE split rule of a masked launch: workspace size (both ws_floats entry points) and launcher ask here
 inline void region_split(const e4s_conv_params& p, int& ksplit, int& cper) {
+    if (region_packed(p)) {
+        const e4s_few_tile::PackGeom g = e4s_few_tile::pack_geom(p.Ha, p.Wa);
+        e4s_few_tile::pack_split((int64_t)e4s_few_tile::pack_tiles(g, p.B) * p.ncls * (p.Cout / 128), p.Cin / 32, ksplit, cper);
+        return;
+    }
     const int64_t tiles = (int64_t)p.B * ((p.Ha + 15) / 16) * ((p.Wa + 15) / 16) * p.ncls * (p.Cout / 128);
     few_tiles_split(tiles, p.Cin / 32, ksplit, cper);
 }
@@ -595,7 +613,13 @@ static_assert(XPIECE * 9 >= XITEMS && XPIECE <= NTHR, "extended halo split");
 // and contract only the pixel tiles that kernel flagged (too many variant rows).  On face-parsing masks no tile is flagged and every block
 // leaves after reading a few flags: ~3 us, where a full grid of early-exiting 512-thread / 150 KB-LDS blocks cost 13-17 us per masked layer
 // (0.23 ms of a batch-8 step, 13 launches).
-template <int WN_, int SPL, bool SCAN = false>
+// PACK: small maps (few_tile_geom.h: 9 images of a 4x4 map, 3 of an 8x8 map per tile; 15/16 resp. 3/4 of the MFMAs of an unpacked tile ran on
+// padding rows).  Row m = (image j, y, x); image j has its own (Ha+2) x (Wa+2) block of the halo array, so the tap offset uses the pitch Wa + 2
+// and a zero ring separates neighbours.  Style, demodulation, noise and label are per ROW (image, region): s_grp holds image * R + region, the
+// row's style fragment comes from global memory once per chunk (the [B][R][Cin] table stays in L2; the LDS slice could not hold 9 x 16 rows),
+// d[image][region] is read per row by the epilogue.  tx_n = images per tile, tiles_per_cls = tiles per class; the K split goes down to one
+// chunk per block (pack_split).  Weight staging, MFMA loop, scheduling pins, stores and the ordered second stage are the unpacked kernel's.
+template <int WN_, int SPL, bool SCAN = false, bool PACK = false>
 __global__ __launch_bounds__(NTHR) void conv_bf16x3_region_kernel(const e4s_conv_params p, const int ntn,
                                                                   const int tx_n, const int per_img,
                                                                   const int tiles_per_cls, const int ksplit,
@@ -603,6 +627,8 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_region_kernel(const e4s_conv
                                                                   const int nblocks) {
     constexpr int WN = WN_, WM = NTHR / 64 / WN, TM = BM / (WM * 32), TN = BN / (WN * 32), NG = 2 * TM;
     static_assert(TM * TN == 4 && (NG == 2 || NG == 4), "wave layout");
+    static_assert(!(SCAN && PACK), "packed launches have no flag table");
+    static_assert(e4s_few_tile::kRows == BM && e4s_few_tile::kHalo == HALO, "few_tile_geom.h describes this tile");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* sA = smem;                          // [2][HALO][ROWB]  fp32 x, 32 channels per row
     unsigned char* sB = smem + 2 * A_BYTES;            // [2][BN][ROWB]    split weights
@@ -635,29 +661,39 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_region_kernel(const e4s_conv
     const int tyb = rem / tx_n, txb = rem - tyb * tx_n;
     const int py = (p.ncls == 4) ? (cls >> 1) : 0, px = (p.ncls == 4) ? (cls & 1) : 0;
     const int R = p.labels ? p.groups_per_batch : 1;
+    const e4s_few_tile::PackGeom geo = e4s_few_tile::pack_geom(PACK ? p.Ha : 0, PACK ? p.Wa : 0);      // (PACK: tt = tile of the class)
+    const int hpitch = PACK ? geo.pitch : HALO_W;
 
     if (tid < BM) {
-        const int ay = tyb * TH + tid / TW, ax = txb * TW + tid % TW;
-        const bool valid = ay < p.Ha && ax < p.Wa;
+        int ay = tyb * TH + tid / TW, ax = txb * TW + tid % TW, img = tb;
+        bool valid = ay < p.Ha && ax < p.Wa;
+        if (PACK) {
+            const e4s_few_tile::PackRow pr = e4s_few_tile::pack_row(geo, tt, tid, p.B);
+            valid = pr.image >= 0;
+            img = valid ? pr.image : 0;
+            ay = pr.y;
+            ax = pr.x;
+        }
         const int oy = ay * p.ostride + py, ox = ax * p.ostride + px;
-        s_out[tid] = valid ? (tb * p.Ho + oy) * p.Wo + ox : -1;
+        s_out[tid] = valid ? (img * p.Ho + oy) * p.Wo + ox : -1;
         float nz = 0.f;
         int r = 0;
         if (valid) {
-            if (p.noise) nz = p.noise_w[0] * p.noise[(int64_t)tb * p.noise_bstride + (int64_t)oy * p.Wo + ox];
+            if (p.noise) nz = p.noise_w[0] * p.noise[(int64_t)img * p.noise_bstride + (int64_t)oy * p.Wo + ox];
             if (p.labels) {   // legacy-nearest lookup of the OUTPUT pixel (F.interpolate 'nearest', model.py:391)
                 const int sy = min((int)floorf((float)oy * ((float)p.Hm / (float)p.Ho)), p.Hm - 1);
                 const int sx = min((int)floorf((float)ox * ((float)p.Wm / (float)p.Wo)), p.Wm - 1);
-                r = p.labels[((size_t)tb * p.Hm + sy) * p.Wm + sx];
+                r = p.labels[((size_t)img * p.Hm + sy) * p.Wm + sx];
             }
+            if (PACK) r += img * R;               // row of the [B][R] style / demodulation tables (dead rows: row 0, never stored)
         }
         s_nz[tid] = nz;
         s_grp[tid] = r;
     }
 
     const int c_lo = ks * cper, nchunk = min(p.Cin / KC - c_lo, cper), nstage = nchunk * 9;      // this block's chunks
-    const float* xb = p.x + (size_t)tb * p.Hi * p.Wi * p.Cin;
-    const float* stab = p.in_scale + (size_t)tb * R * p.Cin;
+    const float* xb = PACK ? p.x : p.x + (size_t)tb * p.Hi * p.Wi * p.Cin;
+    const float* stab = PACK ? p.in_scale : p.in_scale + (size_t)tb * R * p.Cin;
     const unsigned char* wbytes = reinterpret_cast<const unsigned char*>(p.w) + (size_t)cls * 9 * p.Cout * p.Cin * 4;
     const size_t wrow = (size_t)p.Cin * 4;
 
@@ -672,14 +708,22 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_region_kernel(const e4s_conv
         if (item < ITEMS) {
             const int h = item >> 2, q = item & 3;
             const int hy = h / HALO_W, hx = h - hy * HALO_W;
-            const int iy = tyb * TH + hy - 1, ix = txb * TW + hx - 1;
-            it.ok = (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
-            it.src = xb + (it.ok ? ((size_t)iy * p.Wi + ix) * p.Cin : 0) + q * 8;
+            int iy = tyb * TH + hy - 1, ix = txb * TW + hx - 1, img = 0;
+            bool have = true;
+            if (PACK) {                       // slot -> (image, input pixel) of that image's own halo block; slots behind no image are zeroed
+                const e4s_few_tile::PackSlot ps = e4s_few_tile::pack_slot(geo, tt, h, p.B);
+                have = ps.image >= 0;
+                img = have ? ps.image : 0;
+                iy = ps.iy;
+                ix = ps.ix;
+            }
+            it.ok = have && (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
+            it.src = xb + (it.ok ? (((size_t)img * p.Hi + iy) * p.Wi + ix) * p.Cin : 0) + q * 8;
             it.dst = h * ROWB + q * 32;
             it.bufstride = A_BYTES;
         } else {
             const int idx = item - ITEMS, r = idx >> 2, q = idx & 3;
-            it.ok = r < R && item < XITEMS;
+            it.ok = !PACK && r < R && item < XITEMS;          // (PACK: no LDS style slice, the slots are zeroed)
             it.src = stab + (it.ok ? (size_t)r * p.Cin : 0) + q * 8;
             it.dst = S_OFF + (r & (MAXR - 1)) * ROWB + q * 32;
             it.bufstride = S_BYTES;
@@ -720,6 +764,11 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_region_kernel(const e4s_conv
         const int m = (wm * TM + tm) * 32 + li;
         arow[tm] = ((m / TW) * HALO_W + (m % TW)) * ROWB + kh * 32;
         srow[tm] = S_OFF + s_grp[m] * ROWB + kh * 32;
+        if (PACK) {
+            const e4s_few_tile::PackRow pr = e4s_few_tile::pack_row(geo, tt, m, p.B);
+            arow[tm] = (pr.image >= 0 ? e4s_few_tile::pack_arow(geo, pr.j, pr.y, pr.x) : 0) * ROWB + kh * 32;     // (dead rows read slot 0)
+            srow[tm] = s_grp[m] * p.Cin + kh * 8;             // float offset of the row's style in the [B][R][Cin] table
+        }
     }
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) brow[tn] = ((wn * TN + tn) * 32 + li) * ROWB + kh * 16;
@@ -737,7 +786,7 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_region_kernel(const e4s_conv
     int tap = 0, chunk = 0, t1 = 1, c1 = c_lo;       // chunk: relative to c_lo (LDS buffer parity); c1: absolute
 
     for (int s = 0; s < nstage; ++s) {
-        const unsigned char* Ab = sA + (chunk & 1) * A_BYTES + ((tap / 3) * HALO_W + (tap % 3)) * ROWB;
+        const unsigned char* Ab = sA + (chunk & 1) * A_BYTES + ((tap / 3) * hpitch + (tap % 3)) * ROWB;
         const unsigned char* Bb = sB + (s & 1) * B_BYTES;
         auto ldraw = [&](int g) -> f32x8 {            // group g = (kk, tm): 8 fp32 of the lane's pixel
             const int kk = g / TM, tm = g % TM;
@@ -751,6 +800,10 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_region_kernel(const e4s_conv
             for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk) {
+                    if (PACK) {
+                        sv[tm][kk] = load8(p.in_scale + srow[tm] + (c_lo + chunk) * KC + kk * 16);
+                        continue;
+                    }
                     const f32x4 a0 = *reinterpret_cast<const f32x4*>(Sb + srow[tm] + kk * 64);
                     const f32x4 a1 = *reinterpret_cast<const f32x4*>(Sb + srow[tm] + kk * 64 + 16);
                     sv[tm][kk] = f32x8{a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
@@ -842,7 +895,7 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_region_kernel(const e4s_conv
 
     // ---- epilogue: d[region][co] * acc + noise + bias, activation, NHWC store ----
     float* sD = reinterpret_cast<float*>(sA);          // [R][BN]; the loop's last barrier has passed
-    if (p.out_scale) {
+    if (p.out_scale && !PACK) {
         for (int t = tid; t < R * BN; t += NTHR) {
             const int r = t / BN, n = t - r * BN;
             sD[t] = p.out_scale[((size_t)tb * R + r) * p.Cout + n0 + n];
@@ -866,7 +919,7 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_region_kernel(const e4s_conv
                 const int r = 4 * g + i;
                 const int row = (wm * TM + tm) * 32 + i + 8 * g + 4 * kh;
                 const float nz = s_nz[row];
-                const float* drow = sD + s_grp[row] * BN;
+                const float* drow = PACK ? p.out_scale + (size_t)s_grp[row] * p.Cout + n0 : sD + s_grp[row] * BN;     // PACK: d[image][region] per row
 #pragma unroll
                 for (int tn = 0; tn < TN; ++tn) {
                     const int ncol = (wn * TN + tn) * 32 + li;
@@ -897,12 +950,17 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_region_kernel(const e4s_conv
 
 template <int WN_, int SPL>
 int launch_region_v(const e4s_conv_params& p, const int* only_flagged, hipStream_t st) {
-    auto kern = only_flagged ? conv_bf16x3_region_kernel<WN_, SPL, true> : conv_bf16x3_region_kernel<WN_, SPL, false>;
-    static std::atomic<uint64_t> smem_set[2] = {{0}, {0}};
-    if (int e = e4s_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM_REGION, smem_set[only_flagged ? 1 : 0])) return e;
+    const bool pack = region_packed(p);
+    if (pack && only_flagged) return (int)hipErrorInvalidValue;           // packed launches have no rows kernel in front and no flag table
+    auto kern = pack ? conv_bf16x3_region_kernel<WN_, SPL, false, true>
+                     : only_flagged ? conv_bf16x3_region_kernel<WN_, SPL, true> : conv_bf16x3_region_kernel<WN_, SPL, false>;
+    static std::atomic<uint64_t> smem_set[3] = {{0}, {0}, {0}};
+    if (int e = e4s_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM_REGION, smem_set[pack ? 2 : only_flagged ? 1 : 0])) return e;
     const int ntn = p.Cout / BN;
-    const int tx_n = (p.Wa + TW - 1) / TW, per_img = ((p.Ha + TH - 1) / TH) * tx_n;
-    const int tiles_per_cls = p.B * per_img;
+    const e4s_few_tile::PackGeom geo = e4s_few_tile::pack_geom(p.Ha, p.Wa);
+    // packed: tx_n = images per tile, one "tile per image" so that tt is the tile of the class
+    const int tx_n = pack ? geo.n_img : (p.Wa + TW - 1) / TW, per_img = pack ? 1 : ((p.Ha + TH - 1) / TH) * tx_n;
+    const int tiles_per_cls = pack ? e4s_few_tile::pack_tiles(geo, p.B) : p.B * per_img;
     int ksplit, cper;
     region_split(p, ksplit, cper);
     if (ksplit > 1 && !p.splitk_ws) return (int)hipErrorInvalidValue;
@@ -943,11 +1001,15 @@ int launch_region(const e4s_conv_params& p, const int* only_flagged, hipStream_t
 // own A tile -- 256 output pixels x 32 channels, one 128-byte segment per row -- splits it to hi/lo bf16 and stores it
 // next to the weights, both double buffered; the MFMA side is the plain kernel's.  Tile 256 pixels x 128 channels,
 // natural pixel order (tiles may straddle rows and samples), one block per CU.
+// K split (gather_split: 3x3 launches of <= 64 tiles with Cin >= 256 -- the encoder's 512 -> 512 stride-2 conv at 32^2 -> 16^2 is 64
+// tiles of 144 stages): block (ks, tile) contracts all nine taps of the input-channel chunks [ks cper, (ks + 1) cper) and stores its raw
+// sums to slab ks of p.splitk_ws; e4s_splitk_epilogue adds the slabs in order and applies bias / activation.  No epilogue statistics.
 constexpr int GA_BYTES = BM * ROWB;                         // one A stage: 256 rows
 constexpr int SMEM_GATHER = 2 * GA_BYTES + 2 * B_BYTES + BM * 4;
 
 __global__ __launch_bounds__(NTHR) void conv_bf16x3_gather_kernel(const e4s_conv_params p, const int ntn,
-                                                                  const int npix) {
+                                                                  const int npix, const int ntile, const int ksplit,
+                                                                  const int cper) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* sA = smem;                          // [2][BM][ROWB]
     unsigned char* sB = smem + 2 * GA_BYTES;           // [2][BN][ROWB]
@@ -958,9 +1020,11 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_gather_kernel(const e4s_conv
     const int li = lane & 31, kh = lane >> 5;
     const int wm = wave / WN, wn = wave % WN;
     const int logical = xcd_remap(blockIdx.x, gridDim.x);
-    const int mt = logical / ntn, nt = logical - mt * ntn;
+    const int ks = logical / ntile, tile = logical - ks * ntile;          // K split major: an XCD's blocks share their weight chunks
+    const int mt = tile / ntn, nt = tile - mt * ntn;
     const int n0 = nt * BN;
     const int hw = p.Ha * p.Wa;
+    const int c_lo = ks * cper, c_hi = min(p.Cin / KC, c_lo + cper);      // (gather_split leaves no split empty)
 
     if (tid < BM) {
         const int a = mt * BM + tid;
@@ -980,7 +1044,7 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_gather_kernel(const e4s_conv
         a_base[j] = (b * p.Hi + by) * p.Wi + bx;
         a_yx[j] = valid ? ((by << 16) | bx) : 0x7fff7fff;
     }
-    const int ntaps = p.ntaps, nchunk = p.Cin / KC, nstage = ntaps * nchunk;
+    const int ntaps = p.ntaps, nstage = ntaps * (c_hi - c_lo);
     const unsigned char* wbytes = reinterpret_cast<const unsigned char*>(p.w);
     const size_t wrow = (size_t)p.Cin * 4;
     const int bq = (tid & 7) * 16, br0 = tid >> 3;
@@ -1034,10 +1098,10 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_gather_kernel(const e4s_conv
             for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
 
     Pref P;
-    fetch(P, 0, 0);
+    fetch(P, 0, c_lo);
     store(P, 0);
     __syncthreads();
-    int t1 = 0, c1 = 0;                      // stage s + 1
+    int t1 = 0, c1 = c_lo;                   // stage s + 1
     if (++t1 == ntaps) { t1 = 0; ++c1; }
     for (int s = 0; s < nstage; ++s) {
         const unsigned char* Ab = sA + (s & 1) * GA_BYTES;
@@ -1070,7 +1134,7 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_gather_kernel(const e4s_conv
                 acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur], bh[kk][tn], acc[tm][tn], 0, 0, 0);
         };
         if (!cols_live) {                             // (wave-uniform) staging and barriers only
-            fetch(P, more ? t1 : 0, more ? c1 : 0);
+            fetch(P, more ? t1 : 0, more ? c1 : c_lo);
             if (more) store(P, (s + 1) & 1);
             __syncthreads();
             if (++t1 == ntaps) { t1 = 0; ++c1; }
@@ -1080,7 +1144,7 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_gather_kernel(const e4s_conv
         ldA(0, 0);
         __builtin_amdgcn_sched_barrier(0);
         mfma_group(0);
-        fetch(P, more ? t1 : 0, more ? c1 : 0);       // unconditional (dummy stage 0 at the end): waits stay counted
+        fetch(P, more ? t1 : 0, more ? c1 : c_lo);    // unconditional (dummy first stage at the end): waits stay counted
         ldB(1);
         mfma_group(1);
 #pragma unroll
@@ -1098,22 +1162,24 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_gather_kernel(const e4s_conv
         if (++t1 == ntaps) { t1 = 0; ++c1; }
     }
 
-    // ---- epilogue: bias, activation, NHWC store ----
+    // ---- epilogue: bias, activation, NHWC store (K split: the raw sums to this split's slab, same layout as y) ----
+    const bool raw = ksplit > 1;
     float bsv[TN], slp[TN];
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) {
         const int col = n0 + min((wn * TN + tn) * 32 + li, ncols - 1);
-        bsv[tn] = p.bias ? p.bias[col] : 0.f;
-        slp[tn] = (p.act == 2) ? p.slope[col] : p.alpha;
+        bsv[tn] = (p.bias && !raw) ? p.bias[col] : 0.f;
+        slp[tn] = (p.act == 2 && !raw) ? p.slope[col] : p.alpha;
     }
     const float gain = (p.act == 1) ? p.gain : 1.f;
-    const bool do_act = p.act != 0;
-    const bool stats = p.stats_ws != nullptr;         // the launcher guarantees tiles that do not straddle samples
+    const bool do_act = p.act != 0 && !raw;
+    const bool stats = p.stats_ws != nullptr;         // the launcher guarantees tiles that do not straddle samples (and no K split)
     double st_s[TN], st_q[TN];
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) st_s[tn] = st_q[tn] = 0.0;
     const int gycs = p.y_cstride ? p.y_cstride : p.Cout;
     const bool wide = (gycs & 3) == 0;
+    float* const yout = raw ? p.splitk_ws + (size_t)ks * ((size_t)npix * gycs) : p.y;
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) {
 #pragma unroll
@@ -1138,7 +1204,7 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_gather_kernel(const e4s_conv
                 if (off >= 0 && cols_live) {
 #pragma unroll
                     for (int tn = 0; tn < TN; ++tn)
-                        *reinterpret_cast<f32x4*>(p.y + (size_t)off * gycs + n0 + (wn * TN + tn) * 32 + (li & ~3)) =
+                        *reinterpret_cast<f32x4*>(yout + (size_t)off * gycs + n0 + (wn * TN + tn) * 32 + (li & ~3)) =
                             f32x4{v[tn][0], v[tn][1], v[tn][2], v[tn][3]};
                 }
             } else {
@@ -1147,7 +1213,7 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_gather_kernel(const e4s_conv
                     const int off = s_out[(wm * TM + tm) * 32 + i + 8 * g + 4 * kh];
                     if (off < 0 || !cols_live) continue;
 #pragma unroll
-                    for (int tn = 0; tn < TN; ++tn) p.y[(size_t)off * gycs + n0 + (wn * TN + tn) * 32 + li] = v[tn][i];
+                    for (int tn = 0; tn < TN; ++tn) yout[(size_t)off * gycs + n0 + (wn * TN + tn) * 32 + li] = v[tn][i];
                 }
             }
         }
@@ -1178,6 +1244,19 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_gather_kernel(const e4s_conv
     }
 }
 
+// K-split policy of the gather kernel (the workspace size and the launcher both ask here): only the 3x3 launches that leave three quarters
+// of the chip idle AND are deep enough that a split still runs >= 18 stages -- few_tiles_split on <= 64 tiles and >= 8 chunks.  (Cin < 256
+// stays whole: those launches keep their fused epilogue statistics, and their 36 / 72 stages are no longer than one split of the deep ones.)
+void gather_split(const e4s_conv_params& p, int& ksplit, int& cper) {
+    ksplit = 1;
+    cper = p.Cin / KC;
+    const int ycs = p.y_cstride ? p.y_cstride : p.Cout;
+    if (p.ntaps != 9 || p.Cin < 256 || p.Cin % KC || (ycs & 3)) return;
+    const int64_t tiles = (((int64_t)p.B * p.Ha * p.Wa + BM - 1) / BM) * ((p.Cout + BN - 1) / BN);
+    if (tiles <= 0 || tiles > 64) return;
+    few_tiles_split(tiles, p.Cin / KC, ksplit, cper);
+}
+
 int launch_gather(const e4s_conv_params& p, hipStream_t st) {
     auto kern = conv_bf16x3_gather_kernel;
     static std::atomic<uint64_t> smem_set{0};
@@ -1186,10 +1265,13 @@ int launch_gather(const e4s_conv_params& p, hipStream_t st) {
     const int64_t npix = (int64_t)p.B * p.Ha * p.Wa;
     if (npix <= 0) return 0;
     if (npix * ntn >= (1ll << 31)) return (int)hipErrorInvalidValue;
-    const int64_t blocks = ((npix + BM - 1) / BM) * ntn;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NTHR), SMEM_GATHER, st, p, ntn, (int)npix);
+    const int64_t ntile = ((npix + BM - 1) / BM) * ntn;
+    int ksplit, cper;
+    gather_split(p, ksplit, cper);
+    if (ksplit > 1 && (!p.splitk_ws || p.stats_ws)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(ntile * ksplit)), dim3(NTHR), SMEM_GATHER, st, p, ntn, (int)npix, (int)ntile, ksplit, cper);
     E4S_CHECK_LAUNCH();
-    return 0;
+    return ksplit > 1 ? e4s_splitk_epilogue(p, ksplit, st) : 0;
 }
 
 // fp32 rows [rows][cin] -> split rows [rows][cin/32][hi x32 | lo x32] (bf16), same byte size
@@ -1297,6 +1379,7 @@ int e4s_launch_region_select(const e4s_conv_params& p, const int* only_flagged, 
     return launch_region(p, only_flagged, st);
 }
 void e4s_region_split_policy(const e4s_conv_params& p, int& ksplit, int& cper) { region_split(p, ksplit, cper); }
+bool e4s_region_packed(const e4s_conv_params& p) { return region_packed(p); }
 
 extern "C" int e4s_conv_bf16x3_f32(const e4s_conv_params* pp, void* stream) {
     const e4s_conv_params& p = *pp;
@@ -1367,7 +1450,12 @@ int e4s_splitk_epilogue(const e4s_conv_params& p, int ksplit, hipStream_t st) {
 
 extern "C" int64_t e4s_conv_bf16x3_ws_floats(const e4s_conv_params* pp) {
     const e4s_conv_params& p = *pp;
-    if (p.istride != 1 || p.ntaps != 9 || p.Cin % KC) return 0;                  // gather kernels: no split-K
+    if (p.istride == 2 || p.ntaps == 1) {                                         // gather kernel: raw slabs of the deep few-tile 3x3 launches
+        int ksplit, cper;
+        gather_split(p, ksplit, cper);
+        return ksplit > 1 ? (int64_t)ksplit * p.B * p.Ha * p.Wa * (p.y_cstride ? p.y_cstride : p.Cout) : 0;
+    }
+    if (p.istride != 1 || p.ntaps != 9 || p.Cin % KC) return 0;
     if (p.labels) {
         int ksplit, cper;
         region_split(p, ksplit, cper);

@@ -23,6 +23,7 @@
 
 int e4s_launch_region_select(const e4s_conv_params& p, const int* only_flagged, hipStream_t st);      // conv_bf16x3.hip
 void e4s_region_split_policy(const e4s_conv_params& p, int& ksplit, int& cper);                       // conv_bf16x3.hip
+bool e4s_region_packed(const e4s_conv_params& p);                                                     // conv_bf16x3.hip
 bool e4s_region_rows1w_ok(const e4s_conv_params& p);                                                  // conv_region1w.hip
 int e4s_launch_region_rows1w(const e4s_conv_params& p, const void* w16, int* flags, hipStream_t st, int layout);  // conv_region1w.hip
 
@@ -528,6 +529,7 @@ static int region_1w_mode() {
 
 extern "C" int e4s_conv_region_path(const e4s_conv_params* pp) {
     if (!pp || !region_rows_ok(*pp)) return 0;
+    if (e4s_region_packed(*pp)) return 3;          // small maps: several whole images per tile of the region-select kernel
     int ksplit, cper;
     e4s_region_split_policy(*pp, ksplit, cper);
     return (region_1w_mode() && ksplit == 1 && e4s_region_rows1w_ok(*pp)) ? 2 : 1;
@@ -539,7 +541,8 @@ extern "C" int e4s_conv_region_bf16x3_f32(const e4s_conv_params* pp, const void*
     hipStream_t st = as_stream(stream);
     int ksplit, cper;
     e4s_region_split_policy(p, ksplit, cper);
-    if (!w16) return e4s_launch_region_select(p, nullptr, st);
+    // small maps (4^2, 8^2: few_tile_geom.h) go straight to the region-select kernel's packed tiles: no rows kernel, no overflow scan
+    if (!w16 || e4s_region_packed(p)) return e4s_launch_region_select(p, nullptr, st);
     if (!p.splitk_ws) return (int)hipErrorInvalidValue;
     auto kern = conv_region_rows_kernel;
     static std::atomic<uint64_t> smem_set{0};

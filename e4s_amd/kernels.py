@@ -389,7 +389,7 @@ def conv_mfma(x, w, cout, *, plan=None, istride=1, ostride=1, ntaps=9, ncls=1, i
             skws = torch.empty(nws, device=x.device, dtype=torch.float32)
             p.splitk_ws = fptr(skws)
             global LAST_REGION_PATH
-            LAST_REGION_PATH = lib.load().e4s_conv_region_path(ctypes.byref(p))     # 1: 8-wave kernel, 2: one wave per SIMD (tests / bench)
+            LAST_REGION_PATH = lib.load().e4s_conv_region_path(ctypes.byref(p))     # 1: 8-wave kernel, 2: one wave per SIMD, 3: packed small-map tiles (tests / bench)
             call("e4s_conv_region_bf16x3_f32", ctypes.byref(p), ptr(w_split16), stream())
             return y
         nws = lib.load().e4s_conv_bf16x3_ws_floats(ctypes.byref(p))        # split-K partial sums (few-tile launches)
@@ -454,6 +454,19 @@ def want_bf16x3(b, h, w, cin, cout, ncls=1, masked=False):
     return tiles * max(split, 1) >= 64
 
 
+def gather_split(tiles, cin, ntaps):
+    """K splits of a strided (gather-kernel) split-bf16 launch of `tiles` 256-pixel x 128-column tiles (csrc/conv_bf16x3.hip gather_split):
+    3x3, <= 64 tiles, Cin >= 256; every split keeps >= 2 chunks of 32 input channels."""
+    if ntaps != 9 or tiles < 1 or tiles > 64 or cin < 256 or cin % 32:
+        return 1
+    nchunk = cin // 32
+    want = min(nchunk // 2, -(-256 // tiles))
+    if want < 2:
+        return 1
+    cper = -(-nchunk // want)
+    return -(-nchunk // cper)
+
+
 def split_bf16x2(w, out=None):
     """fp32 [..., Cin] -> its split-bf16 image (hi|lo per 32-channel chunk), returned as an opaque fp32-typed tensor of
     the same shape/byte size (only e4s_conv_bf16x3_f32 reads it)."""
@@ -484,7 +497,8 @@ def split16_bf16x2(w, out=None):
 
 
 REGION_1W = os.environ.get("E4S_REGION_1W", "1") != "0"        # mirrors the library's switch (csrc/conv_region.hip)
-LAST_REGION_PATH = 0           # which kernel the last masked launch took (e4s_conv_region_path)
+REGION_PACK = os.environ.get("E4S_REGION_PACK", "1") != "0"    # mirrors the library's switch (csrc/conv_bf16x3.hip): packed small-map tiles
+LAST_REGION_PATH = 0           # which kernel the last masked launch took (e4s_conv_region_path): 1 8-wave rows kernel, 2 one wave per SIMD, 3 packed small-map tiles
 WINO = os.environ.get("E4S_WINO", "1") == "1"        # policy switch of the Winograd F(2,3) kernel (encoders._conv3x3)
 
 

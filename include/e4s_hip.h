@@ -195,7 +195,9 @@ int e4s_upconv_blocks_per_cu(void);    /* diagnostic: occupancy of that kernel a
  *                   encoder's Conv2d(+PReLU) (helpers.py:128-137) and the unmasked StyledConvs incl. the 512^2 / 1024^2
  *                   up-convs (model.py:655-657); column tile 128 / 64 / 32 by Cout
  *   labels != NULL  region-select (per-pixel style on the A fragment): masked StyledConvs (model.py:386-400), plain or
- *                   polyphase; Cout % 128 == 0, in_scale required, act != 2 */
+ *                   polyphase; Cout % 128 == 0, in_scale required, act != 2
+ * Strided (istride = 2, 3x3) and 1x1 launches run the per-tap gather kernel; a 3x3 launch of <= 64 tiles (256 pixels x 128 columns)
+ * with Cin >= 256 splits its input channels over blocks: e4s_conv_bf16x3_ws_floats(p) > 0, p->splitk_ws required, p->stats_ws not allowed. */
 int e4s_conv_bf16x3_f32(const e4s_conv_params* p, void* stream);
 int64_t e4s_conv_bf16x3_ws_floats(const e4s_conv_params* p);
 /* w fp32 [rows][cin] -> out [rows][cin/32][32 hi bf16 | 32 lo bf16] (same byte size), cin % 32 == 0 */
@@ -215,7 +217,10 @@ int e4s_split_bf16x2_f32(const float* w, void* out, int64_t rows, int cin, void*
  * Cout, Cin) bytes (twice the size of w then).
  * Which kernel a launch takes (host-side policy, no launch; ABI v12): e4s_conv_region_path(p) = 0 not covered, 1 the 8-wave kernel
  * (256 pixels x 128 channels per block, two waves per SIMD; with a K split for launches of <= 128 tiles), 2 the one-wave-per-SIMD
- * kernel (csrc/conv_region1w.hip: 256 x 256 tiles, 16 accumulator tiles per wave; Cout % 256 == 0 and no K split). */
+ * kernel (csrc/conv_region1w.hip: 256 x 256 tiles, 16 accumulator tiles per wave; Cout % 256 == 0 and no K split), 3 the region-select
+ * kernel's packed tiles (maps small enough that a 256-row tile holds >= 2 whole images, csrc/few_tile_geom.h: 9 images at 4x4, 3 at 8x8;
+ * K split down to one 32-channel chunk per block; no rows kernel and no overflow scan, with or without w16; E4S_REGION_PACK=0 in the
+ * environment restores paths 1 / 2 for them). */
 int e4s_conv_region_bf16x3_f32(const e4s_conv_params* p, const void* w16, void* stream);
 int64_t e4s_conv_region_ws_floats(const e4s_conv_params* p);
 int e4s_conv_region_path(const e4s_conv_params* p);
