@@ -1,4 +1,4 @@
-// The 128-byte swizzled LDS row that the 32-channel-chunk MFMA convs share (conv_c32.hip, halo_conv3x3.h, retinaface.hip): one
+// The 128-byte swizzled LDS row that the 32-channel-chunk MFMA convs share (conv_c32.hip, halo_conv3x3.h, gather_gemm.h): one
 // 32-channel chunk of a pixel (or of a weight row) per row, as [32 hi | 32 lo] bf16 (split-bf16) or as 32 floats (exact fp32).
 #pragma once
 #include "common.h"

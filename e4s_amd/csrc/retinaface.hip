@@ -3,14 +3,11 @@
 //
 // Conv family (e4s_rconv_f32): 1x1 and 3x3, stride 1 and 2, zero padding k / 2, NHWC fp32, Cin a multiple of 32, Cout of 64, ANY
 // H and W: Ho = (H + 2 pad - k) / s + 1 (ceil(H / 2) at stride 2).  It is an implicit GEMM over the flattened output pixels M = B Ho
-// Wo: a block computes 128 pixels x BN output channels (BN = 128 when Cout allows, else 64), so the input is staged once per 128
-// (64) output channels, not once per 32 -- the 1x1 convs that read up to 2048 channels dominate the network.  Four waves as 2 x 2,
-// each 64 pixels x BN / 2 channels of 32 x 32 MFMA tiles.  K runs over (tap, 32-channel chunk): per step the 128 gathered pixel rows
-// (zero where the tap leaves the image or the row is past M) and the BN weight rows (pre-packed by e4s_rconv_pack_f32) are staged in
-// LDS as 128-byte rows with the 16-byte granule XOR-swizzled, while the next step's global loads are in flight in registers.
-// Arithmetic: split-bf16 (rows hold [32 hi | 32 lo] bf16; three v_mfma_f32_32x32x16_bf16 per product, lo x hi first, fp32
-// accumulate) or exact fp32 (v_mfma_f32_32x32x2_f32) from the same tile code.  The summation order of an output is (tap, chunk,
-// k-step) whatever the batch or the tile's place.  Rows past M are masked at the store.
+// Wo on the tile of gather_gemm.h (RconvGather, RconvEpi below): a block computes 128 pixels x BN output channels (BN = 128 when Cout
+// allows, else 64), so the input is staged once per 128 (64) output channels, not once per 32 -- the 1x1 convs that read up to 2048
+// channels dominate the network.  The gathered pixel rows are zero where the tap leaves the image or the row is past M; the weight
+// rows are pre-packed by e4s_rconv_pack_f32 in row blocks of 64 channels.  Arithmetic: split-bf16 or exact fp32 from the same tile
+// code.  The summation order of an output is (tap, chunk, k-step) whatever the batch or the tile's place.
 //   epilogue  v = acc + bias[c] (eval BatchNorm folded on the host); r0_mode 1: v += r0; act: v = v > 0 ? v : v * slope (slope 0 is
 //             ReLU); r0_mode 2: v += r0.  r0 is an NHWC map at the output resolution, or, with r0_H / r0_W set, a smaller map read
 //             through a nearest upsampling to Ho x Wo (source index min(floor(dst * (float(in) / float(out))), in - 1), ATen's own
@@ -22,14 +19,11 @@
 // Select: score > threshold on the score-sorted list (ties: lower prior index first, from a stable sort), the top_k cut, greedy NMS
 //         as py_cpu_nms.py:18-36 (+ 1 areas, suppression when not ovr <= thresh), keep_top_k, the landmark re-layout to five x then
 //         five y and the final / ss.  One block per image; fixed-capacity outputs and a device count.
-#include "mfma_rows.h"                                          // the swizzled 128-byte row (swz and its bank analysis)
+#include "gather_gemm.h"                                        // the conv family's tile (gather_gemm_kernel) and its weight packer
 
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr int BM = 128, NTHR = 256, YLD = 36, PB = 64;
-constexpr int A_BYTES = BM * ROWB;                                              // 16 384
 
 // ATen's nearest source index (UpSample.h nearest_neighbor_compute_source_index): float scale, floorf, clamp
 __device__ __forceinline__ int nearest_src(int dst, int in, int out) {
@@ -38,204 +32,60 @@ __device__ __forceinline__ int nearest_src(int dst, int in, int out) {
     return s < in - 1 ? s : in - 1;
 }
 
-// F32: 1 = exact fp32 MFMA, 0 = split-bf16; BN: output channels per block (64 or 128)
-template <int F32, int BN>
-__global__ __launch_bounds__(NTHR) void rconv_kernel(const e4s_rconv_params p, const int Ho, const int Wo, const int M) {
-    constexpr int TM = 2, TN = BN / 64;                         // 32 x 32 tiles per wave: 64 pixels x BN / 2 channels
-    constexpr int BJ = BN * 8 / NTHR;                           // 16-byte weight pieces per thread and step
-    constexpr int B_BYTES = BN * ROWB;
-    static_assert(4 * 32 * YLD * 4 <= A_BYTES + B_BYTES, "the output staging tiles alias the operand buffers");
-    __shared__ __attribute__((aligned(16))) unsigned char smem[A_BYTES + B_BYTES];
-    __shared__ int s_out[BM];
-    unsigned char* sA = smem;                                   // [128 pixels][ROWB]
-    unsigned char* sB = smem + A_BYTES;                         // [BN channels][ROWB]
-    float* sY = reinterpret_cast<float*>(smem);                 // [4 waves][32][YLD] output staging (aliases the operands)
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, kh = lane >> 5;
-    const int wm = wave & 1, wn = wave >> 1;
-    const int m0 = blockIdx.x * BM;
-    const int nchunk = p.Cin / KC;
-    const int ntaps = p.k * p.k, pad = p.k >> 1;
-    const int nstep = ntaps * nchunk;
-
-    // this thread's two gathered items: (pixel row m, 8-channel group q)
-    int a_b[2], a_y[2], a_x[2];
-    bool a_live[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int item = tid + NTHR * j;
-        const int m = m0 + (item >> 2);
-        a_live[j] = m < M;
-        const int mm = a_live[j] ? m : 0;
+// Gather of gather_gemm.h: output pixel m = (b, oy, ox) of [B,Ho,Wo] reads input pixel (oy stride - pad + ky, ox stride - pad + kx),
+// k and stride at run time; a tap that leaves the image is not live.
+struct RconvGather {
+    const float* x;
+    int Hi, Wi, x_cstride, k, stride, Ho, Wo;
+    struct Item { int b, y, x, c; bool live; };
+    struct Tap { int ky, kx; };
+    __device__ __forceinline__ int ntaps() const { return k * k; }
+    __device__ __forceinline__ Item item(int m, bool live, int q) const {
+        const int pad = k >> 1;
+        const int mm = live ? m : 0;
         const int ox = mm % Wo, t = mm / Wo;
-        a_x[j] = ox * p.stride - pad;
-        a_y[j] = (t % Ho) * p.stride - pad;
-        a_b[j] = t / Ho;
+        return Item{t / Ho, (t % Ho) * stride - pad, ox * stride - pad, q * 8, live};
     }
-    const f32x8 zero8 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    f32x8 ra[2];
-    f32x4 rb[BJ];
-    auto fetch = [&](int step) {
-        const int tap = step / nchunk, chunk = step - tap * nchunk;
-        const int ky = tap / p.k, kx = tap - ky * p.k;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int iy = a_y[j] + ky, ix = a_x[j] + kx;
-            const bool ok = a_live[j] && (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
-            const size_t off = (((size_t)a_b[j] * p.Hi + (ok ? iy : 0)) * p.Wi + (ok ? ix : 0)) * p.x_cstride + chunk * KC +
-                               ((tid + NTHR * j) & 3) * 8;
-            ra[j] = ok ? load8(p.x + off) : zero8;
-        }
-#pragma unroll
-        for (int j = 0; j < BJ; ++j) {
-            const int i = tid + NTHR * j;
-            const int row = i >> 3;
-            const int cb64 = blockIdx.y * (BN / 64) + (row >> 6);
-            const unsigned char* wb = reinterpret_cast<const unsigned char*>(p.w) +
-                                      (((size_t)cb64 * ntaps + tap) * nchunk + chunk) * (64 * ROWB) + (size_t)(row & 63) * ROWB + (i & 7) * 16;
-            rb[j] = *reinterpret_cast<const f32x4*>(wb);
-        }
-    };
-    auto stage = [&]() {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int item = tid + NTHR * j;
-            const int m = item >> 2, q = item & 3;
-            if (F32) {
-                *reinterpret_cast<f32x4*>(sA + swz(m, 2 * q)) = f32x4{ra[j][0], ra[j][1], ra[j][2], ra[j][3]};
-                *reinterpret_cast<f32x4*>(sA + swz(m, 2 * q + 1)) = f32x4{ra[j][4], ra[j][5], ra[j][6], ra[j][7]};
-            } else {
-                split_store(sA, swz(m, q), ra[j]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < BJ; ++j) {
-            const int i = tid + NTHR * j;
-            *reinterpret_cast<f32x4*>(sB + swz(i >> 3, i & 7)) = rb[j];
-        }
-    };
-
-    if (tid < BM) s_out[tid] = m0 + tid < M ? m0 + tid : -1;
-    int aro[TM], bro[TN];
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm) aro[tm] = swz(wm * 64 + tm * 32 + li, kh);
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) bro[tn] = swz(wn * (BN / 2) + tn * 32 + li, kh);
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
-
-    fetch(0);
-    for (int step = 0; step < nstep; ++step) {
-        __syncthreads();                                        // every reader of the previous step's LDS image is done
-        stage();
-        if (step + 1 < nstep) fetch(step + 1);
-        __syncthreads();
-        if (F32) {
-            // lane (li, kh) holds channels 4 (2 gp + kh) + s of its row, for A and B alike
-#pragma unroll
-            for (int gp = 0; gp < 4; ++gp) {
-                f32x4 a4[TM], b4[TN];
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm) a4[tm] = *reinterpret_cast<const f32x4*>(sA + (aro[tm] ^ (gp * 32)));
-#pragma unroll
-                for (int tn = 0; tn < TN; ++tn) b4[tn] = *reinterpret_cast<const f32x4*>(sB + (bro[tn] ^ (gp * 32)));
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-#pragma unroll
-                    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                        for (int tn = 0; tn < TN; ++tn)
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[tm][s], b4[tn][s], acc[tm][tn], 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm) {
-                    ah[tm] = *reinterpret_cast<const bf16x8*>(sA + (aro[tm] ^ (kk * 32)));
-                    al[tm] = *reinterpret_cast<const bf16x8*>(sA + (aro[tm] ^ (kk * 32) ^ LO));
-                }
-#pragma unroll
-                for (int tn = 0; tn < TN; ++tn) {
-                    bh[tn] = *reinterpret_cast<const bf16x8*>(sB + (bro[tn] ^ (kk * 32)));
-                    bl[tn] = *reinterpret_cast<const bf16x8*>(sB + (bro[tn] ^ (kk * 32) ^ LO));
-                }
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                    for (int tn = 0; tn < TN; ++tn) {
-                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[tm], bh[tn], acc[tm][tn], 0, 0, 0);
-                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bl[tn], acc[tm][tn], 0, 0, 0);
-                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bh[tn], acc[tm][tn], 0, 0, 0);
-                    }
-            }
-        }
+    __device__ __forceinline__ Tap tap(int t) const {
+        const int ky = t / k;
+        return Tap{ky, t - ky * k};
     }
+    __device__ __forceinline__ bool src(const Item& it, const Tap& t, int chunk, const float*& ptr) const {
+        const int iy = it.y + t.ky, ix = it.x + t.kx;
+        const bool ok = it.live && (unsigned)iy < (unsigned)Hi && (unsigned)ix < (unsigned)Wi;
+        ptr = x + (((size_t)it.b * Hi + (ok ? iy : 0)) * Wi + (ok ? ix : 0)) * x_cstride + chunk * KC + it.c;
+        return ok;
+    }
+};
 
-    // ---- epilogue: one 32 x 32 tile per wave and pass through the LDS staging tile, then 16-byte stores ----
-    const bool up = p.r0 && p.r0_H > 0;
-    float* myY = sY + wave * 32 * YLD;
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) {
-            const int co = blockIdx.y * BN + wn * (BN / 2) + tn * 32;
-            const float bsv = p.bias ? p.bias[co + li] : 0.f;
-            __syncthreads();                                    // the operands (or the previous pass's tile) are read
-#pragma unroll
-            for (int r = 0; r < 16; ++r) myY[((r & 3) + 8 * (r >> 2) + 4 * kh) * YLD + li] = acc[tm][tn][r] + bsv;
-            __syncthreads();
-#pragma unroll
-            for (int ps = 0; ps < 4; ++ps) {
-                const int row = ps * 8 + (lane >> 3), c4 = lane & 7;
-                const int pix = s_out[wm * 64 + tm * 32 + row];
-                if (pix < 0) continue;
-                f32x4 v = *reinterpret_cast<const f32x4*>(myY + row * YLD + c4 * 4);
-                f32x4 r = {0.f, 0.f, 0.f, 0.f};
-                if (p.r0) {
-                    size_t rpix = (size_t)pix;
-                    if (up) {
-                        const int ox = pix % Wo, t = pix / Wo;
-                        const int oy = t % Ho, b = t / Ho;
-                        rpix = ((size_t)b * p.r0_H + nearest_src(oy, p.r0_H, Ho)) * p.r0_W + nearest_src(ox, p.r0_W, Wo);
-                    }
-                    r = *reinterpret_cast<const f32x4*>(p.r0 + rpix * p.r0_cstride + co + c4 * 4);
-                }
-                if (p.r0_mode == 1) v = v + r;
-                if (p.act) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * p.slope;
-                }
-                if (p.r0_mode == 2) v = v + r;
-                *reinterpret_cast<f32x4*>(p.y + (size_t)pix * p.y_cstride + p.y_coff + co + c4 * 4) = v;
+// Epi of gather_gemm.h: the epilogue of the file header (bias, r0 before or after the activation, r0 through the nearest upsampling)
+struct RconvEpi {
+    const float* bias_p;                                        // bias [Cout] or null
+    const float* r0;
+    float* y;
+    int Ho, Wo, y_cstride, y_coff, r0_cstride, r0_H, r0_W, r0_mode, act;
+    float slope;
+    __device__ __forceinline__ float bias(int c) const { return bias_p ? bias_p[c] : 0.f; }
+    __device__ __forceinline__ void store(int pix, int c, f32x4 v) const {
+        f32x4 r = {0.f, 0.f, 0.f, 0.f};
+        if (r0) {
+            size_t rpix = (size_t)pix;
+            if (r0_H > 0) {
+                const int ox = pix % Wo, t = pix / Wo;
+                const int oy = t % Ho, b = t / Ho;
+                rpix = ((size_t)b * r0_H + nearest_src(oy, r0_H, Ho)) * r0_W + nearest_src(ox, r0_W, Wo);
             }
+            r = *reinterpret_cast<const f32x4*>(r0 + rpix * r0_cstride + c);
         }
-}
-
-// w [Cout][Cin][k][k] -> [Cout / 64][k k][Cin / 32][64 co][128 bytes]: 32 floats (SPLIT = 0) or [32 hi | 32 lo] bf16 (SPLIT = 1)
-template <int SPLIT>
-__global__ void rconv_pack_kernel(const float* __restrict__ w, unsigned char* __restrict__ out, int Cin, int ntaps, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int ci = (int)(i & 31), co = (int)((i >> 5) & 63);
-    int64_t rest = i >> 11;
-    const int nchunk = Cin / KC;
-    const int chunk = (int)(rest % nchunk);
-    rest /= nchunk;
-    const int tap = (int)(rest % ntaps);
-    const int cb = (int)(rest / ntaps);
-    const float v = w[((size_t)(cb * 64 + co) * Cin + chunk * KC + ci) * ntaps + tap];
-    pack_row_store<SPLIT>(out + (size_t)(i >> 5) * ROWB, ci, v);
-}
+        if (r0_mode == 1) v = v + r;
+        if (act) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * slope;
+        }
+        if (r0_mode == 2) v = v + r;
+        *reinterpret_cast<f32x4*>(y + (size_t)pix * y_cstride + y_coff + c) = v;
+    }
+};
 
 // ---- prep: uint8 BGR HWC -> fp32 NHWC minus the channel means, optionally through a half-pixel bilinear shrink ----
 __global__ __launch_bounds__(256) void prep_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst, int H, int W, int Hd, int Wd,
@@ -447,7 +297,10 @@ int rconv_out(int n, int k, int stride) { return (n + 2 * (k / 2) - k) / stride 
 
 template <int F32, int BN>
 int launch_rconv(const e4s_rconv_params& p, int Ho, int Wo, int M, hipStream_t st) {
-    hipLaunchKernelGGL((rconv_kernel<F32, BN>), dim3((unsigned)((M + BM - 1) / BM), (unsigned)(p.Cout / BN)), dim3(NTHR), 0, st, p, Ho, Wo, M);
+    const RconvGather g = {p.x, p.Hi, p.Wi, p.x_cstride, p.k, p.stride, Ho, Wo};
+    const RconvEpi epi = {p.bias, p.r0, p.y, Ho, Wo, p.y_cstride, p.y_coff, p.r0_cstride, p.r0_H, p.r0_W, p.r0_mode, p.act, p.slope};
+    hipLaunchKernelGGL((gg::gather_gemm_kernel<F32, BN, RconvGather, RconvEpi>), dim3((unsigned)((M + gg::BM - 1) / gg::BM), (unsigned)(p.Cout / BN)),
+                       dim3(gg::NTHR), 0, st, g, epi, p.w, p.Cin / KC, M);
     E4S_CHECK_LAUNCH();
     return 0;
 }
@@ -480,7 +333,7 @@ extern "C" int e4s_rconv_f32(const e4s_rconv_params* pp, void* stream) {
         return (int)hipErrorInvalidValue;
     const int Ho = rconv_out(p.Hi, p.k, p.stride), Wo = rconv_out(p.Wi, p.k, p.stride);
     if (Ho < 1 || Wo < 1) return (int)hipErrorInvalidValue;
-    if ((int64_t)p.B * Ho * Wo >= (1ll << 31) - BM || (int64_t)p.B * p.Hi * p.Wi >= (1ll << 31)) return (int)hipErrorInvalidValue;
+    if ((int64_t)p.B * Ho * Wo >= (1ll << 31) - gg::BM || (int64_t)p.B * p.Hi * p.Wi >= (1ll << 31)) return (int)hipErrorInvalidValue;
     {
         const uintptr_t xa = reinterpret_cast<uintptr_t>(p.x), ya = reinterpret_cast<uintptr_t>(p.y);
         const uintptr_t xe = xa + (size_t)p.B * p.Hi * p.Wi * p.x_cstride * 4, ye = ya + (size_t)p.B * Ho * Wo * p.y_cstride * 4;
@@ -499,10 +352,7 @@ extern "C" int64_t e4s_rconv_pack_bytes(int Cin, int Cout, int k) {
 
 extern "C" int e4s_rconv_pack_f32(const float* w, void* out, int Cin, int Cout, int k, int split, void* stream) {
     if (!w || !out || !aligned16(out) || e4s_rconv_pack_bytes(Cin, Cout, k) == 0) return (int)hipErrorInvalidValue;
-    const int64_t n = (int64_t)Cout * Cin * k * k;
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (split) hipLaunchKernelGGL(rconv_pack_kernel<1>, grid, dim3(256), 0, as_stream(stream), w, static_cast<unsigned char*>(out), Cin, k * k, n);
-    else hipLaunchKernelGGL(rconv_pack_kernel<0>, grid, dim3(256), 0, as_stream(stream), w, static_cast<unsigned char*>(out), Cin, k * k, n);
+    gg::gather_gemm_pack<64>(w, out, Cin, Cout, k * k, (int64_t)Cout * Cin * k * k, split, as_stream(stream));
     E4S_CHECK_LAUNCH();
     return 0;
 }

@@ -2,8 +2,9 @@
 // up-sampling blocks and heads, the soft-argmax head, the anti-alias down-sampling, the 2x2 average pool and the pose kernel.
 //
 // 3-D conv (e4s_conv3d_f32): zero-padded 3x3x3, stride 1, channels-last fp32, Cin a multiple of 32, ANY Cout, D, H and W.  It is a
-// sibling of e4s_rconv_f32, not a user of halo_conv3x3.h: the shipped volumes start at 16 x 4 x 4 and 16 x 8 x 8, where a 16 x 16 halo
-// tile is mostly overhang, and the reshaped input is not plane-contiguous (it arrives through strides).  An implicit GEMM over the
+// private copy of the tile of gather_gemm.h (e4s_rconv_f32's), not a user of halo_conv3x3.h: the shipped volumes start
+// at 16 x 4 x 4 and 16 x 8 x 8, where a 16 x 16 halo tile is mostly overhang, and the reshaped input is not plane-contiguous (it
+// arrives through strides).  An implicit GEMM over the
 // flattened output voxels M = B D Ho Wo: a block computes 128 voxels x BN output channels, BN = 128 / 64 / 32 by the padded Cout
 // (the packer pads Cout to a multiple of 32 with zero rows; padded channels are computed and never stored).  Four waves of 32 x 32
 // MFMA tiles, as 2 x 2 (BN >= 64) or 4 x 1 (BN = 32).  K runs over (tap = (kd, ky, kx), 32-channel chunk): per step the 128 gathered
@@ -33,7 +34,7 @@
 // sum.  The order depends on (D, H, W) only.
 // Pose: one block per frame.  Global average pool (per channel, pixels in rising order), the five linear heads (per output a lane-
 // strided dot and wave_sum), the three 66-bin softmax expectations, the rotation matrix and the keypoint transformation.
-#include "mfma_rows.h"
+#include "gather_gemm.h"                                        // the weight packer (gg::gather_gemm_pack)
 
 #pragma clang fp contract(off)
 
@@ -256,22 +257,6 @@ __global__ __launch_bounds__(NTHR) void conv3d_kernel(const e4s_conv3dx_params p
                 }
             }
         }
-}
-
-// w [Cout][Cin][ntap] (nn.Conv3d) -> [ceil(Cout / 32)][ntap][Cin / 32][32 co][128 bytes]; rows of channels past Cout are zero
-template <int SPLIT>
-__global__ void conv3d_pack_kernel(const float* __restrict__ w, unsigned char* __restrict__ out, int Cin, int Cout, int ntap, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int ci = (int)(i & 31), co = (int)((i >> 5) & 31);
-    int64_t rest = i >> 10;
-    const int nchunk = Cin / KC;
-    const int chunk = (int)(rest % nchunk);
-    rest /= nchunk;
-    const int tap = (int)(rest % ntap);
-    const int c = (int)(rest / ntap) * 32 + co;
-    const float v = c < Cout ? w[((size_t)c * Cin + chunk * KC + ci) * ntap + tap] : 0.f;
-    pack_row_store<SPLIT>(out + (size_t)(i >> 5) * ROWB, ci, v);
 }
 
 template <int F32, int BN>
@@ -498,10 +483,7 @@ extern "C" int e4s_conv3dx_pack_f32(const float* w, void* out, int Cin, int Cout
     if (!w || !out || !aligned16(out) || bytes == 0) return (int)hipErrorInvalidValue;
     const int64_t n = bytes / ROWB * 32;
     if ((n + 255) / 256 >= (1ll << 31)) return (int)hipErrorInvalidValue;
-    const dim3 grid((unsigned)((n + 255) / 256));
-    const int ntap = ksize * ksize * ksize;
-    if (split) hipLaunchKernelGGL(conv3d_pack_kernel<1>, grid, dim3(256), 0, as_stream(stream), w, static_cast<unsigned char*>(out), Cin, Cout, ntap, n);
-    else hipLaunchKernelGGL(conv3d_pack_kernel<0>, grid, dim3(256), 0, as_stream(stream), w, static_cast<unsigned char*>(out), Cin, Cout, ntap, n);
+    gg::gather_gemm_pack<32>(w, out, Cin, Cout, ksize * ksize * ksize, n, split, as_stream(stream));    // nn.Conv3d's [Cout][Cin][ntap], row blocks of 32
     E4S_CHECK_LAUNCH();
     return 0;
 }
