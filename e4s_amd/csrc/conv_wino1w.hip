@@ -15,10 +15,14 @@
 //     the next stage after position 3) are read under the MFMAs of position p; every wave reads the whole V tile (the same LDS read
 //     traffic as A + B fragments of a 64 x 64 wave tile).
 //   * Input transform: 576 items (V-pixel, 4 channels) per chunk = two per thread (A, B) + 64 left over, which are cut into their four
-//     positions so that every thread takes one quarter (Q: wave w computes position w); an item is fetched in the second half of a stage
-//     and transformed + stored in the second half of the next one (A and Q in the chunk's first stage, B in its second).  Addresses are a
-//     per-thread constant + a wave-uniform tile / chunk base, padding is two flag words: no integer multiplies, no branches.
-//   * The issue order is pinned slot by slot (one MFMA + at most one LDS / global instruction + a few VALU, sched_barrier(0)).
+//     positions so that every thread takes one quarter (Q: wave w computes position w).  Addresses are a per-thread constant + a
+//     wave-uniform tile / chunk base, padding is two flag words: no integer multiplies, no branches, no 64-bit vector arithmetic.
+//   * The issue order is pinned slot by slot (one MFMA + an A fragment read or a B fragment load + one PIECE of the input transform,
+//     sched_barrier(0)).  One wave per SIMD means nothing else covers a long MFMA gap (a gap runs max(32, sum of issue costs) cycles, a VALU
+//     instruction costs 4), so the transform is cut into pieces of <= 5 VALU -- one channel of one position, one step of a hi / lo split,
+//     half of a padded pixel's fill, one fetch -- and spread over the chunk's 144 slots: the table is in stage() below;
+//     tools/mfma_gap_report.py prints what the compiler made of it (profiles/r10_wino1w_gaps.txt: the largest gap went from 32 VALU to 6,
+//     the modelled overrun from 17 % to 0.5 %; measured -9 ... -12 % per launch in the step).
 // Split-K launches (<= 128 tiles) and short-K layers stay on conv_wino_kernel.
 #include "common.h"
 #include <stdlib.h>
@@ -62,18 +66,11 @@ struct WTile {
 struct AF { bf16x8 h[4], l[4]; };          // the four 32-row groups of a position
 struct BF { bf16x8 h, l; };                // one position of this wave's 32 channels
 
-// v = (a - m) + sg (b - m) [m = 0, sg = -1: a - b exactly; m = mean, sg = +1: position 1 of the InstanceNorm form], * rs, split to hi / lo bf16
+// v = (a - m) + sg (b - m) [m = 0, sg = -1: a - b exactly; m = mean, sg = +1: position 1 of the InstanceNorm form], * rs: one channel of a quarter item
 template <int XF>
-__device__ __forceinline__ void pair_split(const float a0, const float b0, const float a1, const float b1, const float m0, const float m1,
-                                           const float sg, const float r0, const float r1, unsigned& hi, unsigned& lo) {
-    float v0 = __builtin_fmaf(sg, b0 - m0, a0 - m0), v1 = __builtin_fmaf(sg, b1 - m1, a1 - m1);
-    if (XF == 2) {
-        v0 *= r0;
-        v1 *= r1;
-    }
-    hi = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v0, v1}, bf16x2));
-    const float e0 = v0 - __builtin_bit_cast(float, hi << 16), e1 = v1 - __builtin_bit_cast(float, hi & 0xffff0000u);
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{e0, e1}, bf16x2));
+__device__ __forceinline__ float quarter_v(const float a, const float b, const float m, const float sg, const float r) {
+    const float v = __builtin_fmaf(sg, b - m, a - m);
+    return XF == 2 ? v * r : v;
 }
 
 // XF: 0 plain input, 2 InstanceNorm (x - mean) * rstd folded into the input transform (zero padding applies to the NORMALISED map)
@@ -111,12 +108,15 @@ void conv_wino1w_kernel(const e4s_conv_params p, const int ntn, const int tx_n, 
     // ---- input-transform items.  Item it = (V-pixel v = it >> 2 [row hy = v >> 3 of 18, pair j = v & 7], channels 4 (it & 3) .. + 3) reads the
     // pixels d_i = x[ty0 + hy - 1][tx0 + 2 j - 1 + i], i < 4.  Per thread and class (A: it = tid, B: tid + 256, Q: 512 + lane) the element
     // offset relative to the tile's (ty0, tx0, chunk) origin and the edge flags {hy == 0, hy == 17, j == 0, j == 7} are constants. ----
+    // Offsets are unsigned BYTES from the pixel one row up and one to the left of the tile origin (the smallest address an item reads), so a load
+    // is a wave-uniform 64-bit base + a 32-bit per-lane offset: no 64-bit vector arithmetic in the K loop.
     const int cq = tid & 3;
-    auto rel_of = [&](int v) -> int { return (((v >> 3) - 1) * p.Wi + 2 * (v & 7) - 1) * p.Cin + cq * 4; };
+    const unsigned cin4 = (unsigned)p.Cin * 4u, fb_off = (unsigned)((p.Wi + 1) * p.Cin + cq * 4) * 4u;      // fb_off: the tile's first own pixel
+    auto rel_of = [&](int v) -> unsigned { return (unsigned)(((v >> 3) * p.Wi + 2 * (v & 7)) * p.Cin + cq * 4) * 4u; };
     auto flg_of = [&](int v) -> unsigned { return ((v >> 3) == 0 ? 1u : 0u) | ((v >> 3) == 17 ? 2u : 0u) | ((v & 7) == 0 ? 4u : 0u) | ((v & 7) == 7 ? 8u : 0u); };
     auto dst_of = [&](int v) -> int { return swz(v, cq >> 1) + (cq & 1) * 8; };
     const int vA = tid >> 2, vB = 64 + (tid >> 2), vQ = 128 + (lane >> 2);
-    const int relA = rel_of(vA), relB = rel_of(vB), relQ = rel_of(vQ);
+    const unsigned relA = rel_of(vA), relB = rel_of(vB), relQ = rel_of(vQ);
     const unsigned flgA = flg_of(vA), flgB = flg_of(vB), flgQ = flg_of(vQ);
     const int dstA = dst_of(vA), dstB = dst_of(vB), dstQ = dst_of(vQ) + wave * A_PLANE;      // Q: this wave's position plane
     // quarter items: position = wave: V0 = d0 - d2, V1 = d1 + d2, V2 = d2 - d1, V3 = d1 - d3
@@ -126,57 +126,65 @@ void conv_wino1w_kernel(const e4s_conv_params p, const int ntn, const int tx_n, 
     auto edge_of = [&](const WTile& T) -> unsigned {
         return (T.ty0 == 0 ? 1u : 0u) | (T.ty0 + TH == p.Hi ? 2u : 0u) | (T.tx0 == 0 ? 4u : 0u) | (T.tx0 + TW == p.Wi ? 8u : 0u);
     };
-    auto xbase_of = [&](const WTile& T, int chunk) -> const float* {
-        return p.x + (size_t)T.tb * p.Hi * p.Wi * p.Cin + ((size_t)T.ty0 * p.Wi + T.tx0) * p.Cin + chunk * KC;
+    auto xbase_of = [&](const WTile& T, int chunk) -> const unsigned char* {
+        return reinterpret_cast<const unsigned char*>(p.x + (size_t)T.tb * p.Hi * p.Wi * p.Cin + ((size_t)T.ty0 * p.Wi + T.tx0) * p.Cin + chunk * KC) -
+               (size_t)(p.Wi + 1) * p.Cin * 4;
     };
-    // pixel i of an item: valid unless its row is padding (flags 1 | 2) or it is the left-most / right-most pixel of a border pair
-    auto load_px = [&](const float* xb, int rel, unsigned bad, int i, bool& ok) -> f32x4 {
-        ok = !((bad & 3u) || (i == 0 && (bad & 4u)) || (i == 3 && (bad & 8u)));
-        return *reinterpret_cast<const f32x4*>(xb + (ok ? rel + i * p.Cin : cq * 4));
+    // pixel i of an item: valid unless its row is padding (flags 1 | 2) or it is the left-most / right-most pixel of a border pair.  One mask
+    // test (a short-circuit would put branches into the K loop); `bad` = the item's flags & the tile's edge bits.  The test is two VALU, so the
+    // fill repeats it instead of keeping ten lane masks alive from the fetch to the fill
+    auto px_ok = [&](unsigned flg, unsigned edge, int i) -> bool { return (flg & (edge & (3u | (i == 0 ? 4u : 0u) | (i == 3 ? 8u : 0u)))) == 0u; };
+    auto load_px = [&](const unsigned char* xb, unsigned rel, unsigned flg, unsigned edge, int i) -> f32x4 {
+        return *reinterpret_cast<const f32x4*>(xb + (px_ok(flg, edge, i) ? rel + (unsigned)i * cin4 : fb_off));
     };
     struct Item {
         f32x4 d[4];
-        unsigned okmask;
-    };
-    auto item_load_part = [&](Item& I, const float* xb, int rel, unsigned bad, int i) {
-        bool ok;
-        I.d[i] = load_px(xb, rel, bad, i, ok);
-        if (i == 0) I.okmask = 0;
-        I.okmask |= ok ? (1u << i) : 0u;
     };
     // {mean, rstd} of the thread's four channels (XF == 2); padded pixels -> 0 of the NORMALISED map, i.e. the mean
-    auto stats_of = [&](f32x4& mu, f32x4& rs, int chunk, int par) {
+    auto stats_half = [&](f32x4& mu, f32x4& rs, int chunk, int par, int h) {          // channels 2 h, 2 h + 1 of the thread's four
         if (XF == 2) {
-            const int coff = par * p.Cin * 2 + (chunk * KC + cq * 4) * 2;
-            const f32x4 s0 = *reinterpret_cast<const f32x4*>(s_in + coff);
-            const f32x4 s1 = *reinterpret_cast<const f32x4*>(s_in + coff + 4);
-            mu = f32x4{s0[0], s0[2], s1[0], s1[2]};
-            rs = f32x4{s0[1], s0[3], s1[1], s1[3]};
+            const f32x4 s = *reinterpret_cast<const f32x4*>(s_in + par * p.Cin * 2 + (chunk * KC + cq * 4) * 2 + 4 * h);
+            mu[2 * h] = s[0];
+            rs[2 * h] = s[1];
+            mu[2 * h + 1] = s[2];
+            rs[2 * h + 1] = s[3];
         }
     };
-    auto item_fill = [&](Item& I, const f32x4& mu) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (!(I.okmask & (1u << i))) I.d[i] = XF == 2 ? mu : f32x4{0.f, 0.f, 0.f, 0.f};
+    auto stats_of = [&](f32x4& mu, f32x4& rs, int chunk, int par) {
+        stats_half(mu, rs, chunk, par, 0);
+        stats_half(mu, rs, chunk, par, 1);
     };
-    // position ps (compile time) of an item, channels 2 half .. 2 half + 1: V0 = d0 - d2, V1 = d1 + d2, V2 = d2 - d1, V3 = d1 - d3 (the mean
-    // cancels in the differences; V1 of the InstanceNorm form = (d1 - mu) + (d2 - mu)), * rstd, split to hi / lo
+    // channels 2 h, 2 h + 1 of a padded pixel <- 0 of the (normalised) map
+    auto fill_half = [&](f32x4& d, const f32x4& mu, unsigned flg, unsigned edge, int i, int h) {
+        const bool ok = px_ok(flg, edge, i);
+        d[2 * h] = ok ? d[2 * h] : (XF == 2 ? mu[2 * h] : 0.f);
+        d[2 * h + 1] = ok ? d[2 * h + 1] : (XF == 2 ? mu[2 * h + 1] : 0.f);
+    };
+    // position ps (compile time) of an item, channel c: V0 = d0 - d2, V1 = d1 + d2, V2 = d2 - d1, V3 = d1 - d3 (the mean cancels in the
+    // differences; V1 of the InstanceNorm form = (d1 - mu) + (d2 - mu)), * rstd
+    auto item_v = [&](const Item& I, const f32x4& mu, const f32x4& rs, int ps, int c) -> float {
+        float t;
+        if (ps == 0) t = I.d[0][c] - I.d[2][c];
+        else if (ps == 1) t = XF == 2 ? (I.d[1][c] - mu[c]) + (I.d[2][c] - mu[c]) : I.d[1][c] + I.d[2][c];
+        else if (ps == 2) t = I.d[2][c] - I.d[1][c];
+        else t = I.d[1][c] - I.d[3][c];
+        if (XF == 2) t *= rs[c];
+        return t;
+    };
+    // two channels split to hi / lo bf16, in two steps (a slot each in the K loop): hi and its two values back in fp32; the residuals
+    auto split_hi = [&](float v0, float v1, unsigned& hi, float& h0, float& h1) {
+        hi = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v0, v1}, bf16x2));
+        h0 = __builtin_bit_cast(float, hi << 16);
+        h1 = __builtin_bit_cast(float, hi & 0xffff0000u);
+    };
+    auto split_lo = [&](float v0, float v1, float h0, float h1, unsigned& lo) {
+        lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v0 - h0, v1 - h1}, bf16x2));
+    };
     auto item_pair = [&](const Item& I, const f32x4& mu, const f32x4& rs, int ps, int half, unsigned& hi, unsigned& lo) {
-        float v[2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int c = 2 * half + e;
-            float t;
-            if (ps == 0) t = I.d[0][c] - I.d[2][c];
-            else if (ps == 1) t = XF == 2 ? (I.d[1][c] - mu[c]) + (I.d[2][c] - mu[c]) : I.d[1][c] + I.d[2][c];
-            else if (ps == 2) t = I.d[2][c] - I.d[1][c];
-            else t = I.d[1][c] - I.d[3][c];
-            if (XF == 2) t *= rs[c];
-            v[e] = t;
-        }
-        hi = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v[0], v[1]}, bf16x2));
-        const float e0 = v[0] - __builtin_bit_cast(float, hi << 16), e1 = v[1] - __builtin_bit_cast(float, hi & 0xffff0000u);
-        lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{e0, e1}, bf16x2));
+        const float v0 = item_v(I, mu, rs, ps, 2 * half), v1 = item_v(I, mu, rs, ps, 2 * half + 1);
+        float h0, h1;
+        split_hi(v0, v1, hi, h0, h1);
+        split_lo(v0, v1, h0, h1, lo);
     };
     auto load_stats = [&](const WTile& T, int par) {
         if (XF == 2) {
@@ -200,40 +208,78 @@ void conv_wino1w_kernel(const e4s_conv_params p, const int ntn, const int tx_n, 
     bool has_next = t_next < ntiles;
     WTile nxt = decode(has_next ? t_next : first);
 
-    // ---- prologue (once per block): V of chunk 0, the U planes (0, 0..2) straight to LDS, round 0 = planes (0, 3), (1, 0..2) into registers
-    // (stage 0 stores it), items A and Q of chunk 1 ----
-    Item I;                            // item A / B in flight
+    // ---- prologue (once per block): V of chunk 0 (three rounds of items, the last one on wave 0 only), items A and Q of chunk 1, the B
+    // fragments of stage 0.  EVERY global load is issued before the first wait: the statistics, chunk 0's pixels, the fragments, chunk 1's
+    // items, in the order in which they are consumed (vmcnt counts in order) ----
+    Item IA, IB;                       // items A and B in flight
     f32x4 Qa, Qb;                      // quarter item in flight: the two pixels of this wave's position
-    bool Qoka = true, Qokb = true;
-    I.okmask = 0;
-    load_stats(cur, 0);
-    if (XF == 2) __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) IB.d[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // B fragments.  BPF = 1: one set, position p re-filled for the NEXT stage as soon as its MFMAs have issued (a stage of flight); BPF = 2: three
+    // sets rotating with the vertical tap, position p of the stage AFTER the next fetched under position p of this one
+    BF Bf[BPF == 1 ? 1 : 3][4];
     {
-        const float* xb0 = xbase_of(cur, 0);
+        f32x4 st_r[2];                 // the statistics table: Cin <= 1024 (the launcher refuses more) = at most two rows of four floats per thread
+        if (XF == 2) {
+            const float* st = p.in_stats + (size_t)cur.tb * p.Cin * 2;
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+                if ((tid + r * NTHR) * 4 < p.Cin * 2) st_r[r] = *reinterpret_cast<const f32x4*>(st + (tid + r * NTHR) * 4);
+        }
+        const unsigned char* xb0 = xbase_of(cur, 0);
         const unsigned edge = edge_of(cur);
-        for (int it = tid; it < VROWS * 4; it += NTHR) {
-            const int v = it >> 2;
-            Item I0;
-            f32x4 mu = {0.f, 0.f, 0.f, 0.f}, rs = {1.f, 1.f, 1.f, 1.f};
+        Item I0[3];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) item_load_part(I0, xb0, rel_of(v), flg_of(v) & edge, i);
-            stats_of(mu, rs, 0, 0);
-            item_fill(I0, mu);
+        for (int r = 0; r < 3; ++r) {
+            const int v = (tid + r * NTHR) >> 2;
+            if (r < 2 || wave == 0)
 #pragma unroll
-            for (int ps = 0; ps < 4; ++ps) {
-                unsigned h[2], l[2];
-                item_pair(I0, mu, rs, ps, 0, h[0], l[0]);
-                item_pair(I0, mu, rs, ps, 1, h[1], l[1]);
-                const int a = ps * A_PLANE + dst_of(v);
-                *reinterpret_cast<u32x2*>(sA + a) = u32x2{h[0], h[1]};
-                *reinterpret_cast<u32x2*>(sA + (a ^ 32)) = u32x2{l[0], l[1]};
+                for (int i = 0; i < 4; ++i) I0[r].d[i] = load_px(xb0, rel_of(v), flg_of(v), edge, i);
+        }
+#pragma unroll
+        for (int ps = 0; ps < 4; ++ps) {
+            const unsigned char* b = uf_src(0, 0, ps, cur.n0);
+            Bf[0][ps].h = *reinterpret_cast<const bf16x8*>(b);
+            Bf[0][ps].l = *reinterpret_cast<const bf16x8*>(b + 1024);
+            if constexpr (BPF == 2) {
+                const unsigned char* b1 = uf_src(1, 0, ps, cur.n0);
+                Bf[BPF - 1][ps].h = *reinterpret_cast<const bf16x8*>(b1);
+                Bf[BPF - 1][ps].l = *reinterpret_cast<const bf16x8*>(b1 + 1024);
             }
         }
-        const float* xb1 = xbase_of(cur, 1);
+        const unsigned char* xb1 = xbase_of(cur, 1);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) item_load_part(I, xb1, relA, flgA & edge, i);
-        Qa = load_px(xb1, relQ, flgQ & edge, qa, Qoka);
-        Qb = load_px(xb1, relQ, flgQ & edge, qb, Qokb);
+        for (int i = 0; i < 4; ++i) IA.d[i] = load_px(xb1, relA, flgA, edge, i);
+        Qa = load_px(xb1, relQ, flgQ, edge, qa);
+        Qb = load_px(xb1, relQ, flgQ, edge, qb);
+        if (XF == 2) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+                if ((tid + r * NTHR) * 4 < p.Cin * 2) *reinterpret_cast<f32x4*>(s_in + (tid + r * NTHR) * 4) = st_r[r];
+            __syncthreads();
+        }
+        f32x4 mu = {0.f, 0.f, 0.f, 0.f}, rs = {1.f, 1.f, 1.f, 1.f};
+        stats_of(mu, rs, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int v = (tid + r * NTHR) >> 2;
+            if (r < 2 || wave == 0) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    fill_half(I0[r].d[i], mu, flg_of(v), edge, i, 0);
+                    fill_half(I0[r].d[i], mu, flg_of(v), edge, i, 1);
+                }
+#pragma unroll
+                for (int ps = 0; ps < 4; ++ps) {
+                    unsigned h[2], l[2];
+                    item_pair(I0[r], mu, rs, ps, 0, h[0], l[0]);
+                    item_pair(I0[r], mu, rs, ps, 1, h[1], l[1]);
+                    const int a = ps * A_PLANE + dst_of(v);
+                    *reinterpret_cast<u32x2*>(sA + a) = u32x2{h[0], h[1]};
+                    *reinterpret_cast<u32x2*>(sA + (a ^ 32)) = u32x2{l[0], l[1]};
+                }
+            }
+        }
     }
     __syncthreads();
 
@@ -245,34 +291,21 @@ void conv_wino1w_kernel(const e4s_conv_params p, const int ntn, const int tx_n, 
 
     f32x16 acc[4][4];                 // [position][32-row group]
     AF Af[2];
-    // B fragments.  BPF = 1: one set, position p re-filled for the NEXT stage as soon as its MFMAs have issued (a stage of flight); BPF = 2: three
-    // sets rotating with the vertical tap, position p of the stage AFTER the next fetched under position p of this one
-    BF Bf[BPF == 1 ? 1 : 3][4];
     auto ldA = [&](AF& F, const unsigned char* Abuf, int ps, int ky, int part) {      // part: 2 tm + {0: h, 1: l}
         const unsigned char* a = Abuf + ps * A_PLANE;
         const int tm = part >> 1;
         if (part & 1) F.l[tm] = *reinterpret_cast<const bf16x8*>(a + (aoff[tm][ky] ^ 32));
         else F.h[tm] = *reinterpret_cast<const bf16x8*>(a + aoff[tm][ky]);
     };
-    // fragments of (stage 0, position 0); the B fragments of all of stage 0
+    // fragments of (stage 0, position 0)
 #pragma unroll
     for (int part = 0; part < 8; ++part) ldA(Af[0], sA, 0, 0, part);
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps) {
-        const unsigned char* b = uf_src(0, 0, ps, cur.n0);
-        Bf[0][ps].h = *reinterpret_cast<const bf16x8*>(b);
-        Bf[0][ps].l = *reinterpret_cast<const bf16x8*>(b + 1024);
-        if (BPF == 2) {
-            const unsigned char* b1 = uf_src(1, 0, ps, cur.n0);
-            Bf[1][ps].h = *reinterpret_cast<const bf16x8*>(b1);
-            Bf[1][ps].l = *reinterpret_cast<const bf16x8*>(b1 + 1024);
-        }
-    }
 
     unsigned sg = 0, cg = 0;         // running stage / chunk counters: the LDS buffer parities and the plane ring continue across tiles
     int par = 0;                     // parity of the block's tile counter: s_in[par] holds the current tile's statistics
     f32x4 mu = {0.f, 0.f, 0.f, 0.f}, rs = {1.f, 1.f, 1.f, 1.f};
-    unsigned hh[2], ll[2];
+    float tv[2], th[2], qv[4], qth[4];       // pieces of the input transform in flight between slots
+    unsigned hh[2], ll[2], qh[2], ql[2];
     for (;;) {
         if (has_next) load_stats(nxt, par ^ 1);      // first read when this tile's last chunk stores the next tile's items: barriers in between
         const unsigned edge_c = edge_of(cur), edge_n = edge_of(nxt);
@@ -295,8 +328,8 @@ void conv_wino1w_kernel(const e4s_conv_params p, const int ntn, const int tx_n, 
             const WTile& T2 = in2 ? cur : nxt;
             const int c_2 = in2 ? chunk + 2 : (chunk + 2 - nchunk);
             const unsigned edge_nn = in_tile ? edge_c : edge_n, edge_2 = in2 ? edge_c : edge_n;
-            const float* xb_n = xbase_of(Tn, c_n);              // origin of the next chunk (item B)
-            const float* xb_2 = xbase_of(T2, c_2);              // ... and of the one after (items A, Q)
+            const unsigned char* xb_n = xbase_of(Tn, c_n);              // origin of the next chunk (item B)
+            const unsigned char* xb_2 = xbase_of(T2, c_2);              // ... and of the one after (items A, Q)
             // (a generic lambda per vertical tap: `#pragma unroll` on a loop over this body is refused by the optimizer, and a runtime ts
             // would index aoff[][] dynamically -- scratch)
             auto stage = [&](auto ts_c) {
@@ -332,35 +365,58 @@ void conv_wino1w_kernel(const e4s_conv_params p, const int ntn, const int tx_n, 
                             if (k == 8) Bf[bs_ld][ps].l = *reinterpret_cast<const bf16x8*>(nb + 1024);
                             if (k == 11) Bf[bs_ld][ps].h = *reinterpret_cast<const bf16x8*>(nb);
                         }
-                        if (ps >= 2 && (VAR == 0 || VAR == 1)) {
-                            // ---- second half, slots n = 0..23: the input transform ----
-                            const int n = (ps - 2) * 12 + k;
-                            if (ts < 2 && n < 16) {              // item A (ts 0) / B (ts 1) of the next chunk: per position {pair, pair, store, store}
-                                const int q = n >> 2, piece = n & 3;
-                                if (n == 0) {
-                                    stats_of(mu, rs, c_n, par_n);
-                                    item_fill(I, mu);
-                                }
-                                if (piece == 0) item_pair(I, mu, rs, q, 0, hh[0], ll[0]);
-                                if (piece == 1) item_pair(I, mu, rs, q, 1, hh[1], ll[1]);
-                                const int a = q * A_PLANE + (ts == 0 ? dstA : dstB);
-                                if (piece == 2) *reinterpret_cast<u32x2*>(An + a) = u32x2{hh[0], hh[1]};
-                                if (piece == 3) *reinterpret_cast<u32x2*>(An + (a ^ 32)) = u32x2{ll[0], ll[1]};
+                        if (VAR == 0 || VAR == 1) {
+                            // ---- the input transform, a piece per slot so that no MFMA gap carries more than ~5 VALU (one wave per SIMD:
+                            // nothing else covers a longer gap).  Position P = 4 ts + ps of the chunk's twelve, slot k of its twelve; k 0..7
+                            // also carry an A fragment read, k 8 / 11 a B fragment load, k 9 / 10 nothing else.  Pieces: "fill" = two channels
+                            // of a padded pixel; "V" = one channel of one position; "hi" / "lo" = the two steps of a pair's split.
+                            //   P 0      k 0, 1 {mean, rstd} of the next chunk; k 3..8, 11 (and P 1 k 0) fill A; k 9, 10 fetch item B (pixels 0, 1)
+                            //   P 1      k 1..4 fill Q, k 5..8 V of Q, k 11 hi;                                   k 9, 10 fetch item B (pixels 2, 3)
+                            //   P 2..5   item A, position P - 2: k 0, 1 V, 2 hi, 3 lo, 4, 5 V, 6 hi, 7 lo, k 9 / 10 the two stores
+                            //            (k 8 / 11 of P 2, 3: the rest of Q and its stores; k 8..11 of P 4, 5: fill B)
+                            //   P 6..9   item B, position P - 6, the same; k 8 / 11 of P 6, 7 fetch item A of the chunk after the next, of P 8 Q
+                            // Stores to An lie between the barrier of stage 0 (it releases the buffer the previous chunk read) and the barrier
+                            // of stage 2 (An is first read at P 11); a fetch has >= 47 slots (a stage) of flight before its first use ----
+                            const int P = ts * 4 + ps;
+                            if (P == 0 && k < 2) stats_half(mu, rs, c_n, par_n, k);
+                            {
+                                const int j = P == 0 ? (k >= 3 && k <= 8 ? k - 3 : (k == 11 ? 6 : -1)) : (P == 1 && k == 0 ? 7 : -1);
+                                if (j >= 0) fill_half(IA.d[j >> 1], mu, flgA, edge_nn, j >> 1, j & 1);
                             }
-                            if (ts == 0 && n >= 16 && n < 20) {  // the quarter item: this wave's position of a left-over item
-                                const f32x4 fill = XF == 2 ? mu : f32x4{0.f, 0.f, 0.f, 0.f};
-                                const f32x4 da = Qoka ? Qa : fill, db = Qokb ? Qb : fill;
+                            if (P <= 1 && (k == 9 || k == 10)) IB.d[P * 2 + k - 9] = load_px(xb_n, relB, flgB, edge_nn, P * 2 + k - 9);
+                            // the quarter item: this wave's position of a left-over item
+                            if (P == 1 && (k == 1 || k == 2)) fill_half(Qa, mu, flgQ, edge_nn, qa, k - 1);
+                            if (P == 1 && (k == 3 || k == 4)) fill_half(Qb, mu, flgQ, edge_nn, qb, k - 3);
+                            if (P == 1 && k >= 5 && k <= 8) {
                                 const bool nrm = XF == 2 && wave == 1;
-                                if (n == 16) pair_split<XF>(da[0], db[0], da[1], db[1], nrm ? mu[0] : 0.f, nrm ? mu[1] : 0.f, qsg, rs[0], rs[1], hh[0], ll[0]);
-                                if (n == 17) pair_split<XF>(da[2], db[2], da[3], db[3], nrm ? mu[2] : 0.f, nrm ? mu[3] : 0.f, qsg, rs[2], rs[3], hh[1], ll[1]);
-                                if (n == 18) *reinterpret_cast<u32x2*>(An + dstQ) = u32x2{hh[0], hh[1]};
-                                if (n == 19) *reinterpret_cast<u32x2*>(An + (dstQ ^ 32)) = u32x2{ll[0], ll[1]};
+                                qv[k - 5] = quarter_v<XF>(Qa[k - 5], Qb[k - 5], nrm ? mu[k - 5] : 0.f, qsg, rs[k - 5]);
                             }
-                            // fetches: ts 0: item B of the next chunk; ts 2: items A and Q of the chunk after it
-                            if (ts == 0 && n >= 20) item_load_part(I, xb_n, relB, flgB & edge_nn, n - 20);
-                            if (ts == 2 && n >= 16 && n < 20) item_load_part(I, xb_2, relA, flgA & edge_2, n - 16);
-                            if (ts == 2 && n == 20) Qa = load_px(xb_2, relQ, flgQ & edge_2, qa, Qoka);
-                            if (ts == 2 && n == 21) Qb = load_px(xb_2, relQ, flgQ & edge_2, qb, Qokb);
+                            if (P == 1 && k == 11) split_hi(qv[0], qv[1], qh[0], qth[0], qth[1]);
+                            if (P == 2 && k == 8) split_hi(qv[2], qv[3], qh[1], qth[2], qth[3]);
+                            if (P == 2 && k == 11) split_lo(qv[0], qv[1], qth[0], qth[1], ql[0]);
+                            if (P == 3 && k == 8) {
+                                split_lo(qv[2], qv[3], qth[2], qth[3], ql[1]);
+                                *reinterpret_cast<u32x2*>(An + dstQ) = u32x2{qh[0], qh[1]};
+                            }
+                            if (P == 3 && k == 11) *reinterpret_cast<u32x2*>(An + (dstQ ^ 32)) = u32x2{ql[0], ql[1]};
+                            if (P >= 2 && P <= 9) {               // items A, B of the next chunk
+                                const Item& It = P < 6 ? IA : IB;
+                                const int q = (P - 2) & 3, half = k >> 2;
+                                if (k < 8 && (k & 3) < 2) tv[k & 3] = item_v(It, mu, rs, q, 2 * half + (k & 3));
+                                if (k < 8 && (k & 3) == 2) split_hi(tv[0], tv[1], hh[half], th[0], th[1]);
+                                if (k < 8 && (k & 3) == 3) split_lo(tv[0], tv[1], th[0], th[1], ll[half]);
+                                const int a = q * A_PLANE + (P < 6 ? dstA : dstB);
+                                if (k == 9) *reinterpret_cast<u32x2*>(An + a) = u32x2{hh[0], hh[1]};
+                                if (k == 10) *reinterpret_cast<u32x2*>(An + (a ^ 32)) = u32x2{ll[0], ll[1]};
+                            }
+                            if ((P == 4 || P == 5) && k >= 8) {
+                                const int j = (P - 4) * 4 + k - 8;
+                                fill_half(IB.d[j >> 1], mu, flgB, edge_nn, j >> 1, j & 1);
+                            }
+                            // fetches of the chunk after the next: items A and Q
+                            if ((P == 6 || P == 7) && (k == 8 || k == 11)) IA.d[(P - 6) * 2 + (k == 11 ? 1 : 0)] = load_px(xb_2, relA, flgA, edge_2, (P - 6) * 2 + (k == 11 ? 1 : 0));
+                            if (P == 8 && k == 8) Qa = load_px(xb_2, relQ, flgQ, edge_2, qa);
+                            if (P == 8 && k == 11) Qb = load_px(xb_2, relQ, flgQ, edge_2, qb);
                         }
                         __builtin_amdgcn_sched_barrier(0);
                     }
