@@ -42,7 +42,9 @@ __global__ void adaptive_pool_kernel(const float* __restrict__ x, float* __restr
     y[i] = v;
 }
 
-// dx[b,c,y,x] (+)= sum over the bins that contain the pixel of dy * scale[c] / |bin|; 0 outside the crop
+// dx[b,c,y,x] (+)= sum over the bins that contain the pixel of dy * scale[c] / |bin|; 0 outside the crop.  The bins that contain crop
+// row yc are exactly floor(yc*Ho/Hc) .. ceil((yc+1)*Ho/Hc) - 1: at most 2 when the pool down-samples, about Ho/Hc + 1 when it up-samples
+// (a walk over oy_e - 1 .. oy_e + 1 dropped bins for every Ho > Hc but the x2 ratio).  Added in (oy, ox) ascending order.
 __global__ void adaptive_pool_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, PoolGeom g,
                                          const float* __restrict__ scale, int accumulate, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -62,13 +64,12 @@ __global__ void adaptive_pool_bwd_kernel(const float* __restrict__ dy, float* __
     const int yc = y - g.y0, xc = x - g.x0;
     float acc = 0.f;
     if ((unsigned)yc < (unsigned)g.Hc && (unsigned)xc < (unsigned)g.Wc) {
-        const int oy_e = (int)(((int64_t)yc * g.Ho) / g.Hc), ox_e = (int)(((int64_t)xc * g.Wo) / g.Wc);
-        for (int oy = max(oy_e - 1, 0); oy <= min(oy_e + 1, g.Ho - 1); ++oy) {
+        const int oy_lo = bin_lo(yc, g.Ho, g.Hc), oy_hi = bin_hi(yc, g.Ho, g.Hc);          // the same floor / ceil with the axes swapped
+        const int ox_lo = bin_lo(xc, g.Wo, g.Wc), ox_hi = bin_hi(xc, g.Wo, g.Wc);
+        for (int oy = oy_lo; oy < oy_hi; ++oy) {
             const int ys = bin_lo(oy, g.Hc, g.Ho), ye = bin_hi(oy, g.Hc, g.Ho);
-            if (yc < ys || yc >= ye) continue;
-            for (int ox = max(ox_e - 1, 0); ox <= min(ox_e + 1, g.Wo - 1); ++ox) {
+            for (int ox = ox_lo; ox < ox_hi; ++ox) {
                 const int xs = bin_lo(ox, g.Wc, g.Wo), xe = bin_hi(ox, g.Wc, g.Wo);
-                if (xc < xs || xc >= xe) continue;
                 acc += dy[(((int64_t)b * g.Ho + oy) * g.Wo + ox) * g.C + c] / (float)((ye - ys) * (xe - xs));
             }
         }
@@ -368,6 +369,9 @@ __global__ void lpips_finalize_kernel(const double* __restrict__ part, float* __
 }
 
 // dfx (+)= g * d(d)/d(fx):  n = fx/(r+eps);  dn_c = 2 w_c (nx_c - ny_c) g;  dfx = dn/(r+eps) - fx <dn,fx> / (r (r+eps)^2)
+// A pixel whose fx is all zero (r = 0; a ReLU output can be): <dn,fx> = 0 and fx = 0, so the second term is taken as 0 and
+// dfx = dn/eps, the limit of the closed form.  A deliberate deviation from torch autograd, which differentiates sqrt at 0 and
+// returns NaN there (0 * inf); tests/test_gpu_criteria_kernels.py pins it.
 __global__ void lpips_layer_bwd_kernel(const float* __restrict__ fx, const float* __restrict__ fy, const float* __restrict__ w,
                                        const float* __restrict__ gout, float gmul, float* __restrict__ dfx, int HW, int C,
                                        int accumulate, int64_t npix) {
@@ -510,6 +514,12 @@ PoolGeom make_geom(int B, int C, int Hi, int Wi, int y0, int x0, int Hc, int Wc,
     return g;
 }
 
+// the stem convs index y / dy as [B,Ho,Wo,Cout] without looking: the output grid has to be the one the geometry gives
+bool stem_geom_ok(int B, int Hi, int Wi, int Ho, int Wo, int k, int stride, int pad) {
+    if (B < 1 || Hi < 1 || Wi < 1 || k < 1 || stride < 1 || pad < 0 || Hi + 2 * pad < k || Wi + 2 * pad < k) return false;
+    return Ho == (Hi + 2 * pad - k) / stride + 1 && Wo == (Wi + 2 * pad - k) / stride + 1;
+}
+
 bool geom_ok(const PoolGeom& g) {
     return g.B > 0 && g.C > 0 && g.Ho > 0 && g.Wo > 0 && g.Hc > 0 && g.Wc > 0 && g.y0 >= 0 && g.x0 >= 0 &&
            g.y0 + g.Hc <= g.Hi && g.x0 + g.Wc <= g.Wi;
@@ -540,7 +550,7 @@ extern "C" int e4s_adaptive_pool_bwd_f32(const float* dy, float* dx, int B, int 
 
 extern "C" int e4s_conv_smallcin_f32(const float* x, const float* wp, const float* bias, float* y, int B, int Hi, int Wi,
                                      int Cin, int Ho, int Wo, int Cout, int k, int stride, int pad, int relu, void* stream) {
-    if (Cin < 1 || Cin > 4 || Cout % 16 || k < 1 || stride < 1) return (int)hipErrorInvalidValue;
+    if (Cin < 1 || Cin > 4 || Cout < 16 || Cout % 16 || !stem_geom_ok(B, Hi, Wi, Ho, Wo, k, stride, pad)) return (int)hipErrorInvalidValue;
     const int smem = k * k * Cin * Cout * (int)sizeof(float);
     if (smem > 160 * 1024 - 512 || (k * k * Cin * Cout) % 4) return (int)hipErrorInvalidValue;
     static std::atomic<uint64_t> attr_mask{0};
@@ -557,7 +567,7 @@ extern "C" int e4s_conv_smallcin_f32(const float* x, const float* wp, const floa
 
 extern "C" int e4s_conv_smallcin_bwd_f32(const float* dy, const float* wp, float* dx, int B, int Hi, int Wi, int Cin, int Ho,
                                          int Wo, int Cout, int k, int stride, int pad, void* stream) {
-    if (Cin < 1 || Cin > 4 || Cout % 4 || k < 1 || stride < 1) return (int)hipErrorInvalidValue;
+    if (Cin < 1 || Cin > 4 || Cout < 4 || Cout % 4 || !stem_geom_ok(B, Hi, Wi, Ho, Wo, k, stride, pad)) return (int)hipErrorInvalidValue;
     const int64_t npix = (int64_t)B * Hi * Wi;
     hipLaunchKernelGGL(conv_smallcin_bwd_kernel, grid1(npix), dim3(256), 0, as_stream(stream), dy, wp, dx, B, Hi, Wi, Cin, Ho,
                        Wo, Cout, k, stride, pad, npix);
@@ -570,6 +580,7 @@ extern "C" int e4s_conv_smallcin_col2im_f32(const float* z, float* dx, int B, in
     if (!z || !dx || Cin < 1 || Cin > 4 || k < 1 || stride < 1 || ZC < k * k * Cin) return (int)hipErrorInvalidValue;
     const int64_t npix = (int64_t)B * Hi * Wi;
     if (npix <= 0) return 0;
+    if (!stem_geom_ok(B, Hi, Wi, Ho, Wo, k, stride, pad)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(conv_smallcin_col2im_kernel, grid1(npix), dim3(256), 0, as_stream(stream), z, dx, B, Hi, Wi, Cin, Ho, Wo, ZC, k,
                        stride, pad, npix);
     E4S_CHECK_LAUNCH();

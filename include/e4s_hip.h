@@ -635,11 +635,14 @@ int e4s_grouped_linear_f32(const float* x, const float* W, const float* bias, co
  * F.adaptive_avg_pool2d + BaseNet.z_score of optimization.py:103-106, src/criteria/lpips/networks.py:50-51. */
 int e4s_adaptive_pool_f32(const float* x, float* y, int B, int C, int Hi, int Wi, int y0, int x0, int Hc, int Wc, int Ho,
                           int Wo, int in_nchw, const float* scale, const float* shift, void* stream);
-/* its backward: dx (layout of x) (+)= ...; pixels outside the crop receive 0 */
+/* its backward: dx (layout of x) (+)= ...; pixels outside the crop receive 0.  Any Ho x Wo, smaller or larger than the crop (an up-sampling
+ * pool puts an image pixel into about (Ho/Hc + 1)(Wo/Wc + 1) bins; all of them are added, in (oy, ox) order). */
 int e4s_adaptive_pool_bwd_f32(const float* dy, float* dx, int B, int C, int Hi, int Wi, int y0, int x0, int Hc, int Wc,
                               int Ho, int Wo, int in_nchw, const float* scale, int accumulate, void* stream);
 /* k x k conv of an image with Cin <= 4 channels (AlexNet features[0]: 3 -> 64, k 11, stride 4, pad 2): x NHWC, wp
- * [k*k*Cin][Cout] (tap-major), bias [Cout] or NULL, optional ReLU; Cout % 16 == 0.  *_bwd: the gradient w.r.t. x. */
+ * [k*k*Cin][Cout] (tap-major), bias [Cout] or NULL, optional ReLU; Cout % 16 == 0.  *_bwd: the gradient w.r.t. x (Cout % 4 == 0).
+ * All three stem entry points refuse pad < 0 and an output grid other than Ho = (Hi + 2 pad - k) / stride + 1 (Wo likewise): the kernels
+ * index y / dy / z by Ho, Wo without looking. */
 int e4s_conv_smallcin_f32(const float* x, const float* wp, const float* bias, float* y, int B, int Hi, int Wi, int Cin,
                           int Ho, int Wo, int Cout, int k, int stride, int pad, int relu, void* stream);
 int e4s_conv_smallcin_bwd_f32(const float* dy, const float* wp, float* dx, int B, int Hi, int Wi, int Cin, int Ho, int Wo,
