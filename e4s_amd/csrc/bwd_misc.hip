@@ -4,12 +4,6 @@
 
 namespace {
 
-__device__ __forceinline__ int nearest_src(int dst, int in, int out) {
-    const float scale = (float)in / (float)out;
-    const int s = (int)floorf((float)dst * scale);
-    return s < in - 1 ? s : in - 1;
-}
-
 // dd[b,r,co] = (1/d[b,r,co]) * sum_{p in r} gz[p,co] * (z[p,co] - nw*noise[p] - bias[co]),  z = lrelu^-1(y)/gain
 // (out_pre = d * c  =>  dL/dd = sum gz * c = sum gz * out_pre / d).  Block = (b, 64-channel slab, pixel split).
 constexpr int NPG = 4;

@@ -6,7 +6,9 @@
 #include "e4s_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 #define E4S_CHECK_LAUNCH()                         \
     do {                                           \
@@ -99,3 +101,38 @@ static inline int e4s_ensure_dyn_smem(const void* fn, int bytes, std::atomic<uin
 int e4s_splitk_epilogue(const e4s_conv_params& p, int ksplit, hipStream_t st);
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// grid of 256-thread blocks over n items
+inline dim3 grid1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
+inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
+// 8 consecutive floats as two 16-byte loads
+__device__ __forceinline__ f32x8 load8(const float* src) {
+    const f32x4 lo4 = *reinterpret_cast<const f32x4*>(src);
+    const f32x4 hi4 = *reinterpret_cast<const f32x4*>(src + 4);
+    return f32x8{lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
+}
+
+// The reference's label lookup (F.interpolate(mode='nearest'), model.py:391) = ATen's legacy nearest source index (UpSample.h
+// nearest_neighbor_compute_source_index): float scale, floorf, clamp.  The masked forward, its backward, the plan and ToRGB must agree
+// on it bit for bit: this is the only definition.
+__device__ __forceinline__ int nearest_src(int dst, int in, int out) {
+    const float scale = (float)in / (float)out;
+    const int s = (int)floorf((float)dst * scale);
+    return s < in - 1 ? s : in - 1;
+}
+
+// LDS-only workgroup barrier: every LDS access of this wave issued so far has completed (lgkmcnt(0)); global loads stay in flight
+__device__ __forceinline__ void lds_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// make_coordinate_grid's coordinate of index i of n: 2 (i / (n - 1)) - 1 in float (n = 1: 0 / 0, NaN, as the reference); the product and
+// the difference stay two operations, as in the translation units that use it (they are under `fp contract(off)` as a whole)
+__device__ __forceinline__ float grid_coord(int i, int n) {
+#pragma clang fp contract(off)
+    return 2.f * ((float)i / (float)(n - 1)) - 1.f;
+}

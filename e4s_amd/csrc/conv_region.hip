@@ -12,13 +12,15 @@
 // reads it), scaled with that region's style.  Each lane holds the LDS row of its 2 x 9 (pixel, tap) pairs in registers (own row or
 // a variant row), decided once per tile from the label map; the MFMA loop has no per-fragment arithmetic at all.
 // On face-parsing masks a 16x16 tile of a 64x64 map needs ~70 variant rows on average (max ~170), of a 256x256 map ~17; a tile
-// that needs more than VMAX = 256 is left to the region-select kernel (flag table + a second, filtered launch).
+// that needs more than VMAX = 252 is left to the region-select kernel (flag table + a second, filtered launch).
 //
 // K step: 16 input channels (one v_mfma_f32_32x32x16_bf16 k-step per tap), three taps per pipeline stage, so the halo + variants
-// double-buffer in 2 x 36 KB and the weights in 2 x 24 KB (64-byte swizzled rows, see ROWB below).  Weights come pre-split in the
+// double-buffer in 2 x 36 KB and the weights in 2 x 24 KB (64-byte swizzled rows, rows64.h).  Weights come pre-split in the
 // [tap][Cin/16][Cout][16 hi | 16 lo] layout of e4s_split16_bf16x2_f32: a stage's B tile is three contiguous 8 KB runs.
 // Block = 512 threads = 4 x 2 waves of 64 x 64, tile 256 pixels x 128 output channels, one block per CU (128 KB of LDS).
+// What a tile IS -- row layout, tables, analysis steps 2-4, staging items -- is region_rows.h, shared with conv_region1w.hip.
 #include "common.h"
+#include "region_rows.h"
 #include <stdlib.h>
 
 int e4s_launch_region_select(const e4s_conv_params& p, const int* only_flagged, hipStream_t st);      // conv_bf16x3.hip
@@ -29,70 +31,20 @@ int e4s_launch_region_rows1w(const e4s_conv_params& p, const void* w16, int* fla
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
+using namespace region_rows;        // the tile: TW, TH, HALO, VMAX, NROW, A_BYTES, swz / halo_row / var_row, the tables, the analysis
 
-constexpr int NTHR = 512, BM = 256, BN = 128, TW = 16, TH = 16, HALO_W = TW + 2, HALO = (TH + 2) * HALO_W;
-constexpr int KC = 16;                    // input channels per chunk
-// LDS rows are 64 bytes [16 hi bf16 | 16 lo bf16], UNPADDED; the 16-byte granule index is XORed with (row >> 2) & 3 (round 4; the 80-byte
-// rows of round 3 ran at 37-39 % bank-conflict cycles).  A halo pixel (hy, hx) lives in row hy * 32 + hx: the two 16-lane halves of an
-// MFMA row tile (pixels of two image rows) are then 32 rows apart, so the 16 lanes of every ds_read_b128 group touch 16 different residues
-// mod 16 = 16 different (bank quad, swizzle) pairs for any tap shift -- own-row fragment reads are conflict free.  The 14 unused slots of
-// each 32-row stripe hold the variant rows (18 x 14 = 252 of them).
-constexpr int ROWB = 64, HSTR = 32, VSLOT = HSTR - HALO_W;
-constexpr int VMAX = (TH + 2) * VSLOT, NROW = (TH + 2) * HSTR;
+constexpr int NTHR = 512, BN = 128;
 constexpr int TPS = 3, NSTG = 3;          // taps per stage, stages per chunk
 constexpr int WN = 2, WM = 4, TM = 2, TN = 2;
-constexpr int A_BYTES = NROW * ROWB, B_BYTES = TPS * BN * ROWB;
+constexpr int B_BYTES = TPS * BN * ROWB;
 constexpr int BJ = TPS * BN * 4 / NTHR;   // 16-byte weight pieces per thread and stage (= 3: one per tap)
-constexpr int MAXR = 16;
 static_assert(BJ == TPS && 2 * (HALO + VMAX) <= NSTG * NTHR, "staging split");
 
-__device__ __forceinline__ int swz(int row, int g) { return row * ROWB + ((g ^ ((row >> 2) & 3)) << 4); }
-__device__ __forceinline__ int halo_row(int h) { return (h / HALO_W) * HSTR + h % HALO_W; }          // LDS row of halo pixel h
-__device__ __forceinline__ int var_row(int v) { return (v / VSLOT) * HSTR + HALO_W + v % VSLOT; }    // LDS row of variant row v
-
 constexpr int OFF_B = 2 * A_BYTES;
-constexpr int OFF_OUT = OFF_B + 2 * B_BYTES;        // int   [BM]    output pixel offset or -1
-constexpr int OFF_NZ = OFF_OUT + BM * 4;            // float [BM]    noise term
-constexpr int OFF_NEED = OFF_NZ + BM * 4;           // u32   [HALO]  bit r: a foreign region r reads this halo pixel
-constexpr int OFF_BASE = OFF_NEED + HALO * 4;       // u16   [HALO]  first variant row of the halo pixel
-constexpr int OFF_VAR = OFF_BASE + 656;             // u16   [VMAX]  variant row -> (halo pixel << 4) | region
-constexpr int OFF_LAB = OFF_VAR + VMAX * 2;         // u8    [HALO]  own region of the halo pixel, 0xFF outside the image
-constexpr int OFF_GRP = OFF_LAB + 328;              // u8    [BM]    region of the output pixel
-constexpr int OFF_MISC = OFF_GRP + BM;              // int   [4]
-constexpr int SMEM = OFF_MISC + 16;
+constexpr int OFF_TBL = OFF_B + 2 * B_BYTES;        // the tile tables (region_rows.h)
+constexpr int SMEM = OFF_TBL + TBL_BYTES;
 static_assert(SMEM <= 160 * 1024, "LDS budget");
 static_assert(MAXR * BN * 4 <= A_BYTES, "epilogue table");
-
-__device__ __forceinline__ f32x8 load8(const float* src) {
-    const f32x4 lo4 = *reinterpret_cast<const f32x4*>(src);
-    const f32x4 hi4 = *reinterpret_cast<const f32x4*>(src + 4);
-    return f32x8{lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-}
-
-// a = x * s as hi + lo bf16: hi = rne(x s) (packed convert, re-expanded with a shift / a mask), lo = rne(fma(x, s, -hi))
-__device__ __forceinline__ void scale_split_store(unsigned char* dst, unsigned char* dst_lo, const f32x8 x, const f32x8 s) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 hp;
-    f32x8 res;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const f32x2 xs = f32x2{x[2 * j], x[2 * j + 1]}, ss = f32x2{s[2 * j], s[2 * j + 1]};
-        const f32x2 v = xs * ss;
-        const unsigned h2 = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-        hp[j] = h2;
-        const f32x2 hf = f32x2{__builtin_bit_cast(float, h2 << 16), __builtin_bit_cast(float, h2 & 0xffff0000u)};
-        f32x2 r;
-        asm("v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(r) : "v"(xs), "v"(ss), "v"(hf));
-        res[2 * j] = r[0];
-        res[2 * j + 1] = r[1];
-    }
-    *reinterpret_cast<u32x4*>(dst) = hp;
-    *reinterpret_cast<bf16x8*>(dst_lo) = __builtin_convertvector(res, bf16x8);
-}
 
 __global__ __launch_bounds__(NTHR) void conv_region_rows_kernel(const e4s_conv_params p, const unsigned char* __restrict__ w16,
                                                                 int* __restrict__ tile_flags, const int ntn, const int tx_n,
@@ -101,14 +53,7 @@ __global__ __launch_bounds__(NTHR) void conv_region_rows_kernel(const e4s_conv_p
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* sA = smem;                          // [2][NROW][ROWB]
     unsigned char* sB = smem + OFF_B;                  // [2][TPS*BN][ROWB]
-    int* s_out = reinterpret_cast<int*>(smem + OFF_OUT);
-    float* s_nz = reinterpret_cast<float*>(smem + OFF_NZ);
-    unsigned* s_need = reinterpret_cast<unsigned*>(smem + OFF_NEED);
-    unsigned short* s_base = reinterpret_cast<unsigned short*>(smem + OFF_BASE);
-    unsigned short* s_var = reinterpret_cast<unsigned short*>(smem + OFF_VAR);
-    unsigned char* s_lab = smem + OFF_LAB;
-    unsigned char* s_grp = smem + OFF_GRP;
-    int* s_misc = reinterpret_cast<int*>(smem + OFF_MISC);
+    const TileTables T = tile_tables(smem + OFF_TBL);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -120,22 +65,10 @@ __global__ __launch_bounds__(NTHR) void conv_region_rows_kernel(const e4s_conv_p
     const int logical0 = xcd_remap(blockIdx.x, gridDim.x);
     const int ks = logical0 % ksplit;
     const int logical = logical0 / ksplit;
-    const int mt = logical / ntn, nt = logical - mt * ntn;
+    const Tile tile = decode_tile(p, logical, ntn, tx_n, per_img, tiles_per_cls);
+    const int mt = tile.mt, nt = tile.nt, cls = tile.cls, tb = tile.tb, tyb = tile.tyb, txb = tile.txb, py = tile.py, px = tile.px;
     const int n0 = nt * BN;
-    const int cls = mt / tiles_per_cls;
-    const int tt = mt - cls * tiles_per_cls;
-    const int tb = tt / per_img;
-    const int rem = tt - tb * per_img;
-    const int tyb = rem / tx_n, txb = rem - tyb * tx_n;
-    const int py = (p.ncls == 4) ? (cls >> 1) : 0, px = (p.ncls == 4) ? (cls & 1) : 0;
     const int R = p.groups_per_batch;
-
-    // legacy-nearest label of an OUTPUT pixel (F.interpolate 'nearest', model.py:391)
-    auto label_at = [&](int oy, int ox) -> int {
-        const int sy = min((int)floorf((float)oy * ((float)p.Hm / (float)p.Ho)), p.Hm - 1);
-        const int sx = min((int)floorf((float)ox * ((float)p.Wm / (float)p.Wo)), p.Wm - 1);
-        return p.labels[((size_t)tb * p.Hm + sy) * p.Wm + sx];
-    };
 
     const int nchunk_all = p.Cin / KC, c_lo = ks * cper, nchunk = min(nchunk_all - c_lo, cper);        // this block's chunks
     const float* xb = p.x + (size_t)tb * p.Hi * p.Wi * p.Cin + c_lo * KC;
@@ -173,93 +106,34 @@ __global__ __launch_bounds__(NTHR) void conv_region_rows_kernel(const e4s_conv_p
         const int ay = tyb * TH + tid / TW, ax = txb * TW + tid % TW;
         const bool valid = ay < p.Ha && ax < p.Wa;
         const int oy = ay * p.ostride + py, ox = ax * p.ostride + px;
-        s_out[tid] = valid ? (tb * p.Ho + oy) * p.Wo + ox : -1;
+        T.out[tid] = valid ? (tb * p.Ho + oy) * p.Wo + ox : -1;
         float nz = 0.f;
         int r = 0;
         if (valid) {
             if (p.noise) nz = p.noise_w[0] * p.noise[(int64_t)tb * p.noise_bstride + (int64_t)oy * p.Wo + ox];
-            r = label_at(oy, ox);
+            r = label_at(p, tb, oy, ox);
         }
-        s_nz[tid] = nz;
-        s_grp[tid] = (unsigned char)r;
+        T.nz[tid] = nz;
+        T.grp[tid] = (unsigned char)r;
     }
     if (tid < HALO) {
         const int hy = tid / HALO_W, hx = tid - hy * HALO_W;
         const int iy = tyb * TH + hy - 1, ix = txb * TW + hx - 1;
         const bool inside = (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
-        s_lab[tid] = inside ? (unsigned char)label_at(iy * p.ostride + py, ix * p.ostride + px) : 0xFF;
-        s_need[tid] = 0u;
+        T.lab[tid] = inside ? (unsigned char)label_at(p, tb, iy * p.ostride + py, ix * p.ostride + px) : 0xFF;
+        T.need[tid] = 0u;
     }
     __syncthreads();
-    // ---- 2: which foreign regions read each halo pixel ----
-    if (tid < BM && s_out[tid] >= 0) {
-        const int my = tid / TW, mx = tid % TW;
-        const unsigned r = s_grp[tid];
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int h = (my + tap / 3) * HALO_W + mx + tap % 3;
-            const unsigned lab = s_lab[h];
-            if (lab != 0xFFu && lab != r) atomicOr(&s_need[h], 1u << r);
-        }
-    }
-    __syncthreads();
-    // ---- 3: variant rows of halo pixel h start at HALO + base[h] (exclusive scan of the popcounts, one wave) ----
-    if (wave == 0) {
-        int cnt[6], tot = 0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            const int h = lane * 6 + k;
-            cnt[k] = h < HALO ? __popc(s_need[h]) : 0;
-            tot += cnt[k];
-        }
-        int inc = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
-        }
-        int ex = inc - tot;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            const int h = lane * 6 + k;
-            if (h < HALO) s_base[h] = (unsigned short)min(ex, 65535);
-            ex += cnt[k];
-        }
-        if (lane == 63) s_misc[0] = inc;
-    }
-    __syncthreads();
-    const int nvar = s_misc[0];
-    const bool overflow = nvar > VMAX;
-    if (tid == 0 && nt == 0 && ks == 0) tile_flags[mt] = overflow ? 1 : 0;        // overflowing tiles: the region-select kernel, second launch
-    if (overflow) return;
-    if (tid < HALO) {
-        unsigned bits = s_need[tid];
-        int idx = s_base[tid];
-        while (bits) {
-            const int r = __ffs(bits) - 1;
-            s_var[idx++] = (unsigned short)((tid << 4) | r);
-            bits &= bits - 1;
-        }
-    }
-    __syncthreads();
+    // ---- 2, 3, variant list (region_rows.h); overflowing tiles: the region-select kernel, second launch ----
+    int nvar;
+    if (!variant_rows<NTHR>(T, tid, tid == 0 && nt == 0 && ks == 0, tile_flags + mt, nvar)) return;
 
     // ---- 4: per-lane LDS row of each (pixel, tap) pair; per-thread staging items ----
     int ro[TM][9], brow[TN];
 #pragma unroll
-    for (int tm = 0; tm < TM; ++tm) {
-        const int m = (wm * TM + tm) * 32 + li;
-        const int my = m / TW, mx = m % TW;
-        const unsigned r = s_grp[m];
-        const bool valid = s_out[m] >= 0;
+    for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int h = (my + tap / 3) * HALO_W + mx + tap % 3;
-            const unsigned lab = s_lab[h];
-            int row = halo_row(h);
-            if (valid && lab != 0xFFu && lab != r) row = var_row(s_base[h] + __popc(s_need[h] & ((1u << r) - 1u)));
-            ro[tm][tap] = swz(row, kh);
-        }
-    }
+        for (int tap = 0; tap < 9; ++tap) ro[tm][tap] = tap_row(T, (wm * TM + tm) * 32 + li, tap, kh);
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) brow[tn] = swz((wn * TN + tn) * 32 + li, kh);
 
@@ -267,38 +141,9 @@ __global__ __launch_bounds__(NTHR) void conv_region_rows_kernel(const e4s_conv_p
     int a_src[NSTG], a_sty[NSTG], a_dst[NSTG];
 #pragma unroll
     for (int i = 0; i < NSTG; ++i) {
-        const int e = tid + NTHR * i, j = e >> 1, q = e & 1;
-        int h = -1;
-        unsigned r = 0xFFu;
-        if (j < HALO) {
-            h = j;
-            r = s_lab[h];
-        } else if (j < HALO + nvar) {
-            const unsigned v = s_var[j - HALO];
-            h = v >> 4;
-            r = v & 15u;
-        }
-        a_dst[i] = -1;
-        a_src[i] = a_sty[i] = 0;
-        if (h >= 0) {
-            const int lrow = j < HALO ? halo_row(j) : var_row(j - HALO);
-            if (r == 0xFFu) {                          // outside the image: zero rows, written once
-                const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int b2 = 0; b2 < 2; ++b2) {
-                    *reinterpret_cast<f32x4*>(sA + b2 * A_BYTES + swz(lrow, q)) = z;
-                    *reinterpret_cast<f32x4*>(sA + b2 * A_BYTES + (swz(lrow, q) ^ 32)) = z;
-                }
-            } else {
-                const int hy = h / HALO_W, hx = h - hy * HALO_W;
-                const int iy = tyb * TH + hy - 1, ix = txb * TW + hx - 1;
-                a_src[i] = (iy * p.Wi + ix) * p.Cin + q * 8;
-                a_sty[i] = (int)r * p.Cin + q * 8;
-                a_dst[i] = swz(lrow, q);
-            }
-        }
+        const StageItem it = staging_item<NTHR>(p, T, tile, tid, i, nvar, sA);
+        a_src[i] = it.src, a_sty[i] = it.sty, a_dst[i] = it.dst;
     }
-
 
     // ---- prologue: chunk 0's rows, stage 0's weights ----
 #pragma unroll
@@ -433,8 +278,8 @@ __global__ __launch_bounds__(NTHR) void conv_region_rows_kernel(const e4s_conv_p
             for (int i = 0; i < 4; ++i) {
                 const int r = 4 * g + i;
                 const int row = (wm * TM + tm) * 32 + i + 8 * g + 4 * kh;
-                const float nz = s_nz[row];
-                const float* drow = sD + s_grp[row] * BN;
+                const float nz = T.nz[row];
+                const float* drow = sD + T.grp[row] * BN;
 #pragma unroll
                 for (int tn = 0; tn < TN; ++tn) {
                     const int ncol = (wn * TN + tn) * 32 + li;
@@ -448,7 +293,7 @@ __global__ __launch_bounds__(NTHR) void conv_region_rows_kernel(const e4s_conv_p
             }
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn) quad_transpose4(v[tn][0], v[tn][1], v[tn][2], v[tn][3], li);
-            const int off = s_out[(wm * TM + tm) * 32 + (li & 3) + 8 * g + 4 * kh];
+            const int off = T.out[(wm * TM + tm) * 32 + (li & 3) + 8 * g + 4 * kh];
             if (off >= 0) {
 #pragma unroll
                 for (int tn = 0; tn < TN; ++tn)

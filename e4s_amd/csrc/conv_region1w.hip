@@ -23,22 +23,20 @@
 // instruction = 1 KB contiguous), a tap ahead, into one of three register sets -- no weight ring, no LDS stores or barrier dependence for the
 // weights, no spills; the rows, their staging and the mid-tap barrier are the same.  Measured level with the ring form on the headline launch
 // (0.334-0.342 ms both, one box) and 0-5 % ahead on the polyphase layers; E4S_REGION_1W=3 keeps the ring form selectable.
-// LDS: rows 2 x 36 KB + weights 3 x 16 KB (ring form only) + d[region][256] 16 KB + tile tables = 142 KB.  Row layout, swizzle, variant-row logic, weight image
-// ([tap][Cin/16][Cout][16 hi | 16 lo], e4s_split16_bf16x2_f32) and the flag table for tiles with > VMAX variant rows are conv_region.hip's.
+// LDS: rows 2 x 36 KB + weights 3 x 16 KB (ring form only) + d[region][256] 16 KB + tile tables = 142 KB.  Row layout, swizzle, table block, row table (tap_row) and scale_split_store are
+// region_rows.h, shared with conv_region.hip; the tile decode, the label lookup, analysis steps 2-3 and the staging items are written out here, in the
+// words of that header (measured: DESIGN 3.9 -- with them in shared functions this kernel's prologue changes and the polyphase 512 -> 512 launch loses 0.5-0.8 %); the weight image ([tap][Cin/16][Cout][16 hi | 16 lo], e4s_split16_bf16x2_f32) and the flag table for tiles with > VMAX
+// variant rows are that file's.
 #include "common.h"
+#include "region_rows.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
+using namespace region_rows;        // the tile: TW, TH, HALO, VMAX, NROW, A_BYTES, swz / halo_row / var_row, the tables, tap_row
 
-constexpr int BM = 256, BN = 256, TW = 16, TH = 16, HALO_W = TW + 2, HALO = (TH + 2) * HALO_W;
-constexpr int KC = 16;
-constexpr int ROWB = 64, HSTR = 32, VSLOT = HSTR - HALO_W;
-constexpr int VMAX = (TH + 2) * VSLOT, NROW = (TH + 2) * HSTR;
-constexpr int A_BYTES = NROW * ROWB, B_SLOT = BN * ROWB, NB = 3;
-constexpr int MAXR = 16;
+constexpr int BN = 256;
+constexpr int B_SLOT = BN * ROWB, NB = 3;
 // weight prefetch distance in taps: the weights of tap g + 2 + PFD are fetched during tap g and stored to LDS during tap g + PFD (first read
 // in tap g + 1 + PFD's last group); PFD register sets rotate with the tap index (9 taps per chunk = 0 mod 3)
 #ifndef E4S_1W_PFD
@@ -60,88 +58,13 @@ constexpr int BDPF = E4S_1W_BDPF, ILD = E4S_1W_ILD, IST = E4S_1W_IST;
 static_assert((BDPF == 1 || BDPF == 2) && ILD >= 0 && ILD + 3 < 48 && IST >= 0 && IST + 12 < 48, "B-direct pipeline slots");
 static_assert(PFD == 1 || PFD == 2, "weight prefetch distance");
 
-__device__ __forceinline__ int swz(int row, int g) { return row * ROWB + ((g ^ ((row >> 2) & 3)) << 4); }
-__device__ __forceinline__ int halo_row(int h) { return (h / HALO_W) * HSTR + h % HALO_W; }
-__device__ __forceinline__ int var_row(int v) { return (v / VSLOT) * HSTR + HALO_W + v % VSLOT; }
-
 constexpr int OFF_B = 2 * A_BYTES;
 constexpr int OFF_D = OFF_B + NB * B_SLOT;          // float [MAXR][BN]  d[region][co]
-constexpr int OFF_OUT = OFF_D + MAXR * BN * 4;      // int   [BM]
-constexpr int OFF_NZ = OFF_OUT + BM * 4;            // float [BM]
-constexpr int OFF_NEED = OFF_NZ + BM * 4;           // u32   [HALO]
-constexpr int OFF_BASE = OFF_NEED + HALO * 4;       // u16   [HALO]
-constexpr int OFF_VAR = OFF_BASE + 656;             // u16   [VMAX]
-constexpr int OFF_LAB = OFF_VAR + VMAX * 2;         // u8    [HALO]
-constexpr int OFF_GRP = OFF_LAB + 328;              // u8    [BM]
-constexpr int OFF_MISC = OFF_GRP + BM;              // int   [4]
-constexpr int OFF_DUMMY = (OFF_MISC + 16 + 63) / 64 * 64;      // [64 lanes][64 B]: where the staging stores of items that do not exist go
+constexpr int OFF_TBL = OFF_D + MAXR * BN * 4;       // the tile tables (region_rows.h)
+constexpr int OFF_DUMMY = (OFF_TBL + TBL_BYTES + 63) / 64 * 64;      // [64 lanes][64 B]: where the staging stores of items that do not exist go
 constexpr int SMEM = OFF_DUMMY + 64 * ROWB;
 static_assert(OFF_DUMMY % 64 == 0, "the lo half of a row is at offset ^ 32");
 static_assert(SMEM <= 160 * 1024, "LDS budget");
-
-__device__ __forceinline__ f32x8 load8(const float* src) {
-    const f32x4 lo4 = *reinterpret_cast<const f32x4*>(src);
-    const f32x4 hi4 = *reinterpret_cast<const f32x4*>(src + 4);
-    return f32x8{lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-}
-
-// a = x * s as hi + lo bf16 (conv_region.hip's form: packed convert, shift / mask re-expansion, v_pk_fma with a negated addend)
-__device__ __forceinline__ void scale_split_store(unsigned char* dst, unsigned char* dst_lo, const f32x8 x, const f32x8 s) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 hp;
-    f32x8 res;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const f32x2 xs = f32x2{x[2 * j], x[2 * j + 1]}, ss = f32x2{s[2 * j], s[2 * j + 1]};
-        const f32x2 v = xs * ss;
-        const unsigned h2 = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-        hp[j] = h2;
-        const f32x2 hf = f32x2{__builtin_bit_cast(float, h2 << 16), __builtin_bit_cast(float, h2 & 0xffff0000u)};
-        f32x2 r;
-        asm("v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(r) : "v"(xs), "v"(ss), "v"(hf));
-        res[2 * j] = r[0];
-        res[2 * j + 1] = r[1];
-    }
-    *reinterpret_cast<u32x4*>(dst) = hp;
-    *reinterpret_cast<bf16x8*>(dst_lo) = __builtin_convertvector(res, bf16x8);
-}
-
-// the same split in two halves of plain f32 VALU (no packed-f32 instructions: they cost ~22 cycles each beside MFMAs):
-// hi = rne_bf16(x s) -> 16-byte store; lo = rne_bf16(fma(x, s, -hi)) -> 16-byte store
-__device__ __forceinline__ void split_hi_store(unsigned char* dst, unsigned (&hp)[4], const f32x8 x, const f32x8 s) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float v0 = x[2 * j] * s[2 * j];
-        const float v1 = x[2 * j + 1] * s[2 * j + 1];
-        hp[j] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v0, v1}, bf16x2));
-    }
-    *reinterpret_cast<u32x4*>(dst) = u32x4{hp[0], hp[1], hp[2], hp[3]};
-}
-__device__ __forceinline__ void split_lo_store(unsigned char* dst, const unsigned (&hp)[4], const f32x8 x, const f32x8 s) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    unsigned lp[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float h0 = __builtin_bit_cast(float, hp[j] << 16), h1 = __builtin_bit_cast(float, hp[j] & 0xffff0000u);
-        const float r0 = __builtin_fmaf(x[2 * j], s[2 * j], -h0), r1 = __builtin_fmaf(x[2 * j + 1], s[2 * j + 1], -h1);
-        lp[j] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, bf16x2));
-    }
-    *reinterpret_cast<u32x4*>(dst) = u32x4{lp[0], lp[1], lp[2], lp[3]};
-}
-
-// LDS-only workgroup barrier: every LDS access of this wave issued so far has completed (lgkmcnt(0)); global loads stay in flight
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 
 struct Frag { bf16x8 h, l; };
 
@@ -166,14 +89,7 @@ void conv_region_rows1w_kernel(const e4s_conv_params p, const unsigned char* __r
     unsigned char* sA = smem;                          // [2][NROW][ROWB]
     unsigned char* sB = smem + OFF_B;                  // [NB][BN][ROWB]
     float* sD = reinterpret_cast<float*>(smem + OFF_D);
-    int* s_out = reinterpret_cast<int*>(smem + OFF_OUT);
-    float* s_nz = reinterpret_cast<float*>(smem + OFF_NZ);
-    unsigned* s_need = reinterpret_cast<unsigned*>(smem + OFF_NEED);
-    unsigned short* s_base = reinterpret_cast<unsigned short*>(smem + OFF_BASE);
-    unsigned short* s_var = reinterpret_cast<unsigned short*>(smem + OFF_VAR);
-    unsigned char* s_lab = smem + OFF_LAB;
-    unsigned char* s_grp = smem + OFF_GRP;
-    int* s_misc = reinterpret_cast<int*>(smem + OFF_MISC);
+    const TileTables T = tile_tables(smem + OFF_TBL);
 
     const int tid = threadIdx.x;
     [[maybe_unused]] unsigned long long tstamp[5];
@@ -192,7 +108,7 @@ void conv_region_rows1w_kernel(const e4s_conv_params p, const unsigned char* __r
     const int tyb = rem / tx_n, txb = rem - tyb * tx_n;
     const int py = (p.ncls == 4) ? (cls >> 1) : 0, px = (p.ncls == 4) ? (cls & 1) : 0;
     const int R = p.groups_per_batch;
-
+    // tile decode and label lookup: region_rows.h's decode_tile / label_at (= common.h's nearest_src), written out (see the file comment)
     auto label_at = [&](int oy, int ox) -> int {          // legacy-nearest label of an OUTPUT pixel (model.py:391)
         const int sy = min((int)floorf((float)oy * ((float)p.Hm / (float)p.Ho)), p.Hm - 1);
         const int sx = min((int)floorf((float)ox * ((float)p.Wm / (float)p.Wo)), p.Wm - 1);
@@ -253,29 +169,31 @@ void conv_region_rows1w_kernel(const e4s_conv_params p, const unsigned char* __r
             hl[k] = label_at(hin[k] ? iy * p.ostride + py : 0, hin[k] ? ix * p.ostride + px : 0);
         }
         if (is_px) {
-            s_out[tid] = valid ? (tb * p.Ho + oy) * p.Wo + ox : -1;
-            s_nz[tid] = (valid && p.noise) ? p.noise_w[0] * nzr : 0.f;
-            s_grp[tid] = (unsigned char)(valid ? rr : 0);
+            T.out[tid] = valid ? (tb * p.Ho + oy) * p.Wo + ox : -1;
+            T.nz[tid] = (valid && p.noise) ? p.noise_w[0] * nzr : 0.f;
+            T.grp[tid] = (unsigned char)(valid ? rr : 0);
         }
 #pragma unroll
         for (int k = 0; k < HPT; ++k) {
             const int h = tid + k * NTHR;
             if (h < HALO) {
-                s_lab[h] = hin[k] ? (unsigned char)hl[k] : 0xFF;
-                s_need[h] = 0u;
+                T.lab[h] = hin[k] ? (unsigned char)hl[k] : 0xFF;
+                T.need[h] = 0u;
             }
         }
     }
     __syncthreads();
+    // ---- 2, 3, variant list (region_rows.h); overflowing tiles: the region-select kernel, second launch ----
+    // ---- 2, 3, variant list: region_rows.h's variant_rows<NTHR>, written out (see the file comment) ----
     // ---- 2: which foreign regions read each halo pixel ----
-    if (tid < BM && s_out[tid] >= 0) {
+    if (tid < BM && T.out[tid] >= 0) {
         const int my = tid / TW, mx = tid % TW;
-        const unsigned r = s_grp[tid];
+        const unsigned r = T.grp[tid];
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int h = (my + tap / 3) * HALO_W + mx + tap % 3;
-            const unsigned lab = s_lab[h];
-            if (lab != 0xFFu && lab != r) atomicOr(&s_need[h], 1u << r);
+            const unsigned lab = T.lab[h];
+            if (lab != 0xFFu && lab != r) atomicOr(&T.need[h], 1u << r);
         }
     }
     __syncthreads();
@@ -285,7 +203,7 @@ void conv_region_rows1w_kernel(const e4s_conv_params p, const unsigned char* __r
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
             const int h = lane * 6 + k;
-            cnt[k] = h < HALO ? __popc(s_need[h]) : 0;
+            cnt[k] = h < HALO ? __popc(T.need[h]) : 0;
             tot += cnt[k];
         }
         int inc = tot;
@@ -298,22 +216,22 @@ void conv_region_rows1w_kernel(const e4s_conv_params p, const unsigned char* __r
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
             const int h = lane * 6 + k;
-            if (h < HALO) s_base[h] = (unsigned short)min(ex, 65535);
+            if (h < HALO) T.base[h] = (unsigned short)min(ex, 65535);
             ex += cnt[k];
         }
-        if (lane == 63) s_misc[0] = inc;
+        if (lane == 63) T.misc[0] = inc;
     }
     __syncthreads();
-    const int nvar = s_misc[0];
+    const int nvar = T.misc[0];
     const bool overflow = nvar > VMAX;
     if (tid == 0 && nt == 0) tile_flags[mt] = overflow ? 1 : 0;        // overflowing tiles: the region-select kernel, second launch
     if (overflow) return;
     for (int h = tid; h < HALO; h += NTHR) {
-        unsigned bits = s_need[h];
-        int idx = s_base[h];
+        unsigned bits = T.need[h];
+        int idx = T.base[h];
         while (bits) {
             const int r = __ffs(bits) - 1;
-            s_var[idx++] = (unsigned short)((h << 4) | r);
+            T.var[idx++] = (unsigned short)((h << 4) | r);
             bits &= bits - 1;
         }
     }
@@ -323,20 +241,9 @@ void conv_region_rows1w_kernel(const e4s_conv_params p, const unsigned char* __r
     // ---- 4: per-lane LDS row of each (pixel, tap) pair; per-thread staging items ----
     int ro[TM][9];
 #pragma unroll
-    for (int tm = 0; tm < TM; ++tm) {
-        const int m = (wm * TM + tm) * 32 + li;
-        const int my = m / TW, mx = m % TW;
-        const unsigned r = s_grp[m];
-        const bool valid = s_out[m] >= 0;
+    for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int h = (my + tap / 3) * HALO_W + mx + tap % 3;
-            const unsigned lab = s_lab[h];
-            int row = halo_row(h);
-            if (valid && lab != 0xFFu && lab != r) row = var_row(s_base[h] + __popc(s_need[h] & ((1u << r) - 1u)));
-            ro[tm][tap] = swz(row, kh);
-        }
-    }
+        for (int tap = 0; tap < 9; ++tap) ro[tm][tap] = tap_row(T, (wm * TM + tm) * 32 + li, tap, kh);
     // 1 x 4 waves (TM = 8): the 72 row offsets (< 2^16 each) packed two per register (groups 2 j and 2 j + 1) -- 36 registers instead of 72
     unsigned rop[TM / 2][9];
 #pragma unroll
@@ -358,14 +265,15 @@ void conv_region_rows1w_kernel(const e4s_conv_params p, const unsigned char* __r
     unsigned a_srcb[NIT], a_styb[NIT];         // the same as byte offsets (32-bit voffset beside a wave-uniform base)
 #pragma unroll
     for (int i = 0; i < NIT; ++i) {
+        // region_rows.h's staging_item<NTHR>, written out (see the file comment)
         const int e = tid + NTHR * i, j = e >> 1, q = e & 1;
         int h = -1;
         unsigned r = 0xFFu;
         if (j < HALO) {
             h = j;
-            r = s_lab[h];
+            r = T.lab[h];
         } else if (j < HALO + nvar) {
-            const unsigned v = s_var[j - HALO];
+            const unsigned v = T.var[j - HALO];
             h = v >> 4;
             r = v & 15u;
         }
@@ -389,7 +297,6 @@ void conv_region_rows1w_kernel(const e4s_conv_params p, const unsigned char* __r
             }
         }
     }
-
 #pragma unroll
     for (int i = 0; i < NIT; ++i) {
         a_srcb[i] = (unsigned)a_src[i] * 4u;
@@ -664,10 +571,10 @@ void conv_region_rows1w_kernel(const e4s_conv_params p, const unsigned char* __r
             for (int i = 0; i < 4; ++i) {
                 const int r = 4 * g + i;
                 const int row = (wm * TM + tm) * 32 + i + 8 * g + 4 * kh;
-                const float nz = s_nz[row];
+                const float nz = T.nz[row];
                 float d4[TN];
                 {
-                    const float* dp = sD + ((s_grp[row] * WN + wn) * 32 + li) * TN;
+                    const float* dp = sD + ((T.grp[row] * WN + wn) * 32 + li) * TN;
                     if (TN == 4) {
                         const f32x4 v4 = *reinterpret_cast<const f32x4*>(dp);
 #pragma unroll
@@ -688,7 +595,7 @@ void conv_region_rows1w_kernel(const e4s_conv_params p, const unsigned char* __r
             }
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn) quad_transpose4(v[tn][0], v[tn][1], v[tn][2], v[tn][3], li);
-            const int off = s_out[(wm * TM + tm) * 32 + (li & 3) + 8 * g + 4 * kh];
+            const int off = T.out[(wm * TM + tm) * 32 + (li & 3) + 8 * g + 4 * kh];
             if (off >= 0) {
 #pragma unroll
                 for (int tn = 0; tn < TN; ++tn)

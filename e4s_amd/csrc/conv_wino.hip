@@ -31,6 +31,7 @@
 // stages of chunk c, three waves per stage, rotating through the eight.
 // Persistent (grid = min(tiles, CUs); the pipeline runs through the tile boundary) and split-K for launches of <= 128 tiles.
 #include "common.h"
+#include "rows64.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -38,13 +39,15 @@ int e4s_launch_wino1w(const e4s_conv_params& p, int ntn, int tx_n, int per_img, 
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int NTHR = 512;
 constexpr int TH = 16, TW = 16, NPAIR = TW / 2;
 constexpr int VROWS = (TH + 2) * NPAIR;          // 144 V-pixels per position and chunk
-constexpr int BN = 128, KC = 16, ROWB = 64;
+constexpr int BN = 128;
+using rows64::KC;
+using rows64::ROWB;
+using rows64::swz;          // 64-byte swizzled rows [16 hi | 16 lo]
 constexpr int A_PLANE = VROWS * ROWB, A_BYTES = 4 * A_PLANE;        // 36 864
 constexpr int B_PLANE = BN * ROWB, B_BYTES = 4 * B_PLANE;           // 32 768
 #ifndef E4S_WINO_READS_FIRST
@@ -57,8 +60,6 @@ constexpr int B_PLANE = BN * ROWB, B_BYTES = 4 * B_PLANE;           // 32 768
 constexpr int WT_MIN_CHUNKS = 32;
 constexpr int NITEMS = VROWS * 4;                                   // 576 (V-pixel, 4-channel group) items per chunk
 constexpr int SMEM_WINO = 2 * A_BYTES + 2 * B_BYTES + 4 * BN * 2 * 8;       // + Cin * 16 bytes of {mean, rstd} tables when XF == 2 (launcher)
-
-__device__ __forceinline__ int swz(int row, int g) { return row * ROWB + ((g ^ ((row >> 2) & 3)) << 4); }
 
 // hi / lo split of 4 floats -> two 8-byte LDS stores
 __device__ __forceinline__ void split_store4(unsigned char* hi_dst, unsigned char* lo_dst, const f32x4 v) {

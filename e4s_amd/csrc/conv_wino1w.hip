@@ -25,12 +25,12 @@
 //     the modelled overrun from 17 % to 0.5 %; measured -9 ... -12 % per launch in the step).
 // Split-K launches (<= 128 tiles) and short-K layers stay on conv_wino_kernel.
 #include "common.h"
+#include "rows64.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -38,7 +38,10 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 constexpr int NTHR = 256;
 constexpr int TH = 16, TW = 16, NPAIR = TW / 2;
 constexpr int VROWS = (TH + 2) * NPAIR;          // 144 V-pixels per position and chunk
-constexpr int BN = 128, KC = 16, ROWB = 64;
+constexpr int BN = 128;
+using rows64::KC;
+using rows64::ROWB;
+using rows64::swz;          // 64-byte swizzled rows [16 hi | 16 lo]
 constexpr int A_PLANE = VROWS * ROWB, A_BYTES = 4 * A_PLANE;        // 36 864
 constexpr int OFF_IN = 2 * A_BYTES;                                 // XF == 2: float [2 tile parities][Cin][{mean, rstd}]
 constexpr int SMEM_1W = OFF_IN;
@@ -49,15 +52,6 @@ constexpr int SMEM_1W = OFF_IN;
 // encoder convs 6.95 vs 6.85 ms, step 16.40 vs 16.31 ms (profiles/r06_wino1w.json) -- one stage of flight covers the weight stream
 constexpr int BPF = E4S_WINO_BPF;
 static_assert(BPF == 1 || BPF == 2, "B prefetch distance");
-
-__device__ __forceinline__ int swz(int row, int g) { return row * ROWB + ((g ^ ((row >> 2) & 3)) << 4); }
-
-// LDS-only workgroup barrier: every LDS access of this wave issued so far has completed (lgkmcnt(0)); global loads stay in flight
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 
 struct WTile {
     int n0, tb, ty0, tx0, slot;

@@ -9,8 +9,6 @@
 
 namespace {
 
-inline dim3 grid1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 // ---- adaptive average pooling of a crop (F.adaptive_avg_pool2d bins: start = floor(o*in/out), end = ceil((o+1)*in/out)) --
 __device__ __forceinline__ int bin_lo(int o, int in, int out) { return (int)(((int64_t)o * in) / out); }
 __device__ __forceinline__ int bin_hi(int o, int in, int out) { return (int)((((int64_t)o + 1) * in + out - 1) / out); }

@@ -24,12 +24,6 @@
 
 namespace {
 
-__device__ __forceinline__ int nearest_src(int dst, int in, int out) {        // F.interpolate(mode='nearest'), model.py:391
-    const float scale = (float)in / (float)out;
-    const int s = (int)floorf((float)dst * scale);
-    return s < in - 1 ? s : in - 1;
-}
-
 // u[(ph), b, a, c] = gz[b, p, c] * d[b * R + r(p), c];  NCLS == 1: p = a (same layout);  NCLS == 4: gz is [B, 2H, 2W, C], u is [4][B, H, W, C]
 __global__ __launch_bounds__(256) void region_scale_kernel(const float* __restrict__ gz, const float* __restrict__ d,
                                                            const uint8_t* __restrict__ labels, int Hm, int Wm, int R, float* __restrict__ u,

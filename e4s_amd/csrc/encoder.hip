@@ -448,12 +448,6 @@ __global__ __launch_bounds__(512) void finalize_se_kernel(const double* __restri
     se_body(pooled, hidden, fc1, fc2, gate + (int64_t)b * C, C, Cr);
 }
 
-__device__ __forceinline__ int nearest_src(int dst, int in, int out) {
-    const float scale = (float)in / (float)out;
-    const int s = (int)floorf((float)dst * scale);
-    return s < in - 1 ? s : in - 1;
-}
-
 // ---- regional average pooling, two stages.  Stage 1: block = (sample, 64-channel slab, range of RM_PIX pixels); 16 lanes x float4
 // walk the slab's 64 channels, 16 pixel groups, and every thread keeps R running float4 sums in LDS columns it alone touches.  The
 // block adds its 16 pixel groups in order and writes one partial [R][64] (+ the R pixel counts) to the workspace.  Stage 2 adds the

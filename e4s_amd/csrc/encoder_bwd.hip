@@ -7,12 +7,6 @@
 
 namespace {
 
-__device__ __forceinline__ int nearest_src(int dst, int in, int out) {
-    const float scale = (float)in / (float)out;
-    const int s = (int)floorf((float)dst * scale);
-    return s < in - 1 ? s : in - 1;
-}
-
 // ---- InstanceNorm backward, stage 1: per (b, c): A = sum_p dy, Bq = sum_p dy * xhat, xhat = (x - mean) * rstd ----------
 __global__ void in_bwd_partial_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                       const float* __restrict__ stats, double* __restrict__ ws, int HW, int C, int nsplit) {
@@ -219,8 +213,6 @@ __global__ void region_mean_bwd_kernel(const float* __restrict__ dcodes, const u
     if (accumulate) v += *reinterpret_cast<const f32x4*>(dfeat + i * 4);
     *reinterpret_cast<f32x4*>(dfeat + i * 4) = v;
 }
-
-inline dim3 grid1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 int in_nsplit(int B, int HW, int C) {
     int nsplit = 2048 / (B * (C / 64) > 0 ? B * (C / 64) : 1);

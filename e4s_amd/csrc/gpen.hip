@@ -106,8 +106,6 @@ __global__ void minibatch_stddev_kernel(const float* __restrict__ x, float* __re
     }
 }
 
-inline dim3 grid1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 }  // namespace
 
 extern "C" int e4s_conv1x1_small_f32(const float* x, const float* w, const float* bias, float* y, int B, int HW, int Cin,

@@ -5,9 +5,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-
 constexpr int KC = 32, ROWB = 128, LO = 64;                                     // channels per chunk, bytes per row, offset of the lo halves
 
 // byte offset of 16-byte granule g (0..7) of row r.  split-bf16: granules 0..3 hold 8 hi channels each, g + 4 (the same offset ^ 64)
@@ -33,12 +30,6 @@ __device__ __forceinline__ void split_store(unsigned char* base, int off, const 
     *reinterpret_cast<bf16x8*>(base + (off ^ LO)) = l;
 }
 
-__device__ __forceinline__ f32x8 load8(const float* src) {
-    const f32x4 lo4 = *reinterpret_cast<const f32x4*>(src);
-    const f32x4 hi4 = *reinterpret_cast<const f32x4*>(src + 4);
-    return f32x8{lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-}
-
 // element ci of a packed (unswizzled, global-memory) weight row: 32 floats (SPLIT = 0) or [32 hi | 32 lo] bf16 (SPLIT = 1)
 template <int SPLIT>
 __device__ __forceinline__ void pack_row_store(unsigned char* row, int ci, float v) {
@@ -51,7 +42,5 @@ __device__ __forceinline__ void pack_row_store(unsigned char* row, int ci, float
         reinterpret_cast<float*>(row)[ci] = v;
     }
 }
-
-inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 }  // namespace

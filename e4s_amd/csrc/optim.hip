@@ -353,8 +353,6 @@ __global__ void ema_kernel(float* __restrict__ dst, const float* __restrict__ sr
     dst[i] = __fmaf_rn(src[i], omd, a);
 }
 
-inline dim3 grid1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 int linear_t_nsplit(int R, int O, int K) {
     const int kblk = (K + 255) / 256;
     int ns = 2048 / (R * kblk > 0 ? R * kblk : 1);

@@ -13,8 +13,6 @@
 
 namespace {
 
-inline dim3 grid1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 struct Taps8 { float k[8]; };
 
 __device__ __forceinline__ int reflect_idx(int i, int n) {

@@ -54,13 +54,6 @@ __global__ __launch_bounds__(256) void mask_labels_vec4_kernel(const float* __re
     if (!clean || ones[0] != 1 || ones[1] != 1 || ones[2] != 1 || ones[3] != 1) atomicOr(flags, 1);
 }
 
-// legacy 'nearest' source index (F.interpolate(mode='nearest')): min(floor(dst * in/out), in-1)
-__device__ __forceinline__ int nearest_src(int dst, int in, int out) {
-    const float scale = (float)in / (float)out;
-    const int s = (int)floorf((float)dst * scale);
-    return s < in - 1 ? s : in - 1;
-}
-
 struct PlanGeom {
     int B, R, Hm, Wm, Ha, Wa, nphase, BM;
 };

@@ -155,8 +155,6 @@ __global__ void paste_kernel(const uint8_t* __restrict__ face, const uint8_t* __
     }
 }
 
-inline dim3 grid1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 }  // namespace
 
 extern "C" int e4s_onehot_u8_f32(const uint8_t* labels, float* out, int B, int R, int H, int W, void* stream) {

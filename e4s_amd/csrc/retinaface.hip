@@ -25,13 +25,6 @@
 
 namespace {
 
-// ATen's nearest source index (UpSample.h nearest_neighbor_compute_source_index): float scale, floorf, clamp
-__device__ __forceinline__ int nearest_src(int dst, int in, int out) {
-    const float scale = (float)in / (float)out;
-    const int s = (int)floorf((float)dst * scale);
-    return s < in - 1 ? s : in - 1;
-}
-
 // Gather of gather_gemm.h: output pixel m = (b, oy, ox) of [B,Ho,Wo] reads input pixel (oy stride - pad + ky, ox stride - pad + kx),
 // k and stride at run time; a tap that leaves the image is not live.
 struct RconvGather {

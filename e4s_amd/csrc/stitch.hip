@@ -27,8 +27,6 @@ __device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }     
 __device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
 __device__ __forceinline__ float sub_rn(float a, float b) { return a - b; }
 
-inline dim3 grid1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 __device__ __forceinline__ int reflect101(int i, int n) {        // cv::BORDER_REFLECT_101: gfedcb|abcdefgh|gfedcba
     if (n == 1) return 0;
     while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;

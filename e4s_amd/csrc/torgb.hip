@@ -6,12 +6,6 @@
 
 namespace {
 
-__device__ __forceinline__ int nearest_src(int dst, int in, int out) {
-    const float scale = (float)in / (float)out;
-    const int s = (int)floorf((float)dst * scale);
-    return s < in - 1 ? s : in - 1;
-}
-
 // LP lanes cooperate on one pixel (each 4 channels per step); 64/LP pixels per wave step.  LP = 8 / 16 / 32 for Cin < 64 / < 128 / < 256;
 // Cin >= 256 (a whole wave per pixel) is torgb_wide_kernel below.
 template <int LP>

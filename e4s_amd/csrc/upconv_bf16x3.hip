@@ -34,8 +34,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
 
 constexpr int PKC = 32;                                    // input channels per chunk of the weight PACK (a K stage takes half a chunk)
 constexpr int KC = 16, ROWB = 80, LO = 32;                 // LDS rows: [16 hi | 16 lo | 16 bytes of padding] (80 = 16 x 5: conflict free)
@@ -66,12 +64,6 @@ __device__ __forceinline__ void split_store(unsigned char* dst, const f32x8 v) {
     const bf16x8 l = __builtin_convertvector(r, bf16x8);
     *reinterpret_cast<bf16x8*>(dst) = h;
     *reinterpret_cast<bf16x8*>(dst + LO) = l;
-}
-
-__device__ __forceinline__ f32x8 load8(const float* src) {
-    const f32x4 lo4 = *reinterpret_cast<const f32x4*>(src);
-    const f32x4 hi4 = *reinterpret_cast<const f32x4*>(src + 4);
-    return f32x8{lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
 }
 
 struct TileId { int tb, ty, tx, nt; };

@@ -273,9 +273,6 @@ int launch_conv3d(const e4s_conv3dx_params& p, int Ho, int Wo, int M, int cout_p
 // ---- soft-argmax head ----
 constexpr int SA_N = 13;                                        // sum, x, y, z and nine jacobian entries
 
-// make_coordinate_grid's coordinate of index i of n: 2 (i / (n - 1)) - 1 in float (n = 1: 0 / 0, NaN, as the reference)
-__device__ __forceinline__ float grid_coord(int i, int n) { return 2.f * ((float)i / (float)(n - 1)) - 1.f; }
-
 __global__ __launch_bounds__(256) void softargmax_kernel(const float* __restrict__ logits, int64_t l_bstride, int64_t l_kstride,
                                                          int64_t l_vstride, const float* __restrict__ jac, int64_t j_bstride,
                                                          int64_t j_cstride, int64_t j_vstride, int njmaps, int K, int D, int H, int W,

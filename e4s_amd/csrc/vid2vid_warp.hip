@@ -19,8 +19,6 @@ namespace {
 
 constexpr int MAXG = 32;                                        // keypoints + 1 a thread keeps in registers
 
-__device__ __forceinline__ float grid_coord(int i, int n) { return 2.f * ((float)i / (float)(n - 1)) - 1.f; }
-
 // grid_sample's source index of coordinate g on an axis of n voxels (align_corners=False), clamped to [-2, n + 1]: every index
 // below -1 or above n samples nothing but padding, so the clamp changes no result and keeps the integer conversion in range
 __device__ __forceinline__ float unnormalize(float g, int n) {
@@ -240,7 +238,6 @@ __global__ __launch_bounds__(256) void scale_rows_kernel(float* __restrict__ y, 
     reinterpret_cast<f32x4*>(y)[i] = reinterpret_cast<f32x4*>(y)[i] * m[i / C4];
 }
 
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 inline bool grid_ok(int64_t n) { return n >= 1 && (n + 255) / 256 < (1ll << 31); }
 inline bool volume_ok(int B, int D, int H, int W) { return B >= 1 && D >= 1 && H >= 1 && W >= 1 && (int64_t)B * D * H * W < (1ll << 31); }
 
@@ -251,7 +248,7 @@ extern "C" int e4s_bnrelu3d_f32(const float* x, int64_t x_bstride, int64_t x_dst
     if (!x || !scale || !shift || !y || !volume_ok(B, D, H, W) || C < 4 || C % 4) return (int)hipErrorInvalidValue;
     if (x_bstride < 0 || x_dstride < 0 || x_ystride < 0 || x_xstride < C) return (int)hipErrorInvalidValue;
     if (x_bstride % 4 || x_dstride % 4 || x_ystride % 4 || x_xstride % 4) return (int)hipErrorInvalidValue;
-    if (!al16(x) || !al16(scale) || !al16(shift) || !al16(y)) return (int)hipErrorInvalidValue;
+    if (!aligned16(x) || !aligned16(scale) || !aligned16(shift) || !aligned16(y)) return (int)hipErrorInvalidValue;
     const int64_t n = (int64_t)B * D * H * W * (C / 4);
     if (!grid_ok(n)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(bnrelu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), x, x_bstride, x_dstride, x_ystride,
@@ -274,7 +271,7 @@ extern "C" int e4s_sparse_warp_f32(const float* feat, int feat_batch, const floa
                                    const float* jac, float* y, int y_cstride, int N, int K, int D, int H, int W, int C, float variance,
                                    void* stream) {
     if (!feat || !kp_source || !kp_driving || !y || !volume_ok(N, D, H, W) || K < 1 || K + 1 > MAXG) return (int)hipErrorInvalidValue;
-    if (C != 4 || y_cstride < 5 * (K + 1) || !(variance > 0.f) || !al16(feat)) return (int)hipErrorInvalidValue;
+    if (C != 4 || y_cstride < 5 * (K + 1) || !(variance > 0.f) || !aligned16(feat)) return (int)hipErrorInvalidValue;
     if ((feat_batch != 1 && feat_batch != N) || (kp_batch != 1 && kp_batch != N)) return (int)hipErrorInvalidValue;
     const int64_t n = (int64_t)N * D * H * W * (K + 1);
     if (!grid_ok(n)) return (int)hipErrorInvalidValue;
@@ -297,7 +294,7 @@ extern "C" int e4s_motion_combine_f32(const float* logits, int l_cstride, const 
 
 extern "C" int e4s_warp3d_f32(const float* vol, int64_t v_dstride, int64_t v_ystride, int64_t v_xstride, const float* deformation, float* y,
                               int N, int D, int H, int W, int C, void* stream) {
-    if (!vol || !deformation || !y || !volume_ok(N, D, H, W) || C < 4 || C % 4 || !al16(vol) || !al16(y)) return (int)hipErrorInvalidValue;
+    if (!vol || !deformation || !y || !volume_ok(N, D, H, W) || C < 4 || C % 4 || !aligned16(vol) || !aligned16(y)) return (int)hipErrorInvalidValue;
     if (v_dstride < 0 || v_ystride < 0 || v_xstride < C || v_dstride % 4 || v_ystride % 4 || v_xstride % 4) return (int)hipErrorInvalidValue;
     const int64_t n = (int64_t)N * D * H * W * (C / 4);
     if (!grid_ok(n)) return (int)hipErrorInvalidValue;
@@ -310,7 +307,7 @@ extern "C" int e4s_warp3d_f32(const float* vol, int64_t v_dstride, int64_t v_yst
 extern "C" int e4s_occlusion_f32(const float* x, int x_cstride, const float* w, const float* bias, float* out, int N, int D, int H, int W,
                                  int C, int ksize, void* stream) {
     if (!x || !w || !out || !volume_ok(N, D, H, W) || C < 4 || C % 4 || x_cstride < C || x_cstride % 4) return (int)hipErrorInvalidValue;
-    if (ksize < 1 || !(ksize & 1) || ksize > 15 || !al16(x) || !al16(w)) return (int)hipErrorInvalidValue;
+    if (ksize < 1 || !(ksize & 1) || ksize > 15 || !aligned16(x) || !aligned16(w)) return (int)hipErrorInvalidValue;
     if ((int64_t)ksize * ksize * D * (C / 4) >= (1ll << 31)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(occlusion_kernel, dim3((unsigned)((int64_t)N * H * W)), dim3(256), 0, as_stream(stream), x, x_cstride, w, bias, out, D, H,
                        W, C / 4, ksize);
@@ -319,7 +316,7 @@ extern "C" int e4s_occlusion_f32(const float* x, int x_cstride, const float* w, 
 }
 
 extern "C" int e4s_scale_rows_f32(float* y, const float* m, int64_t rows, int C, void* stream) {
-    if (!y || !m || rows < 1 || C < 4 || C % 4 || !al16(y)) return (int)hipErrorInvalidValue;
+    if (!y || !m || rows < 1 || C < 4 || C % 4 || !aligned16(y)) return (int)hipErrorInvalidValue;
     const int64_t n = rows * (C / 4);
     if (!grid_ok(n)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), y, m, C / 4, n);

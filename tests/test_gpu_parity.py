@@ -13,6 +13,7 @@ import torch.nn.functional as F
 
 from e4s_amd import synth
 from oracle import e4s_oracle as orc
+from region_cases import region_case as _region_case
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -282,31 +283,6 @@ def test_region_kernel_split_k_vs_fp32(res, cin, cout, up, monkeypatch):
     assert torch.equal(y, K.conv_mfma(x, wt, cout, w_split=ws, **kw))
     ref = K.conv_mfma(x, wt, cout, **kw)
     assert 0 < maxabs(y, ref) < 1e-4 * float(ref.abs().max())
-
-
-def _region_case(b, h, w, cin, cout, up, kind, R=12, seed=41):
-    from e4s_amd import kernels as K
-    g = torch.Generator().manual_seed(seed)
-    ncls = 4 if up else 1
-    ho, wo = (2 * h, 2 * w) if up else (h, w)
-    x = torch.randn(b, h, w, cin, generator=g).to(DEV)
-    wt = torch.randn(ncls, 9, cout, cin, generator=g).to(DEV) / math.sqrt(cin * 9)
-    if kind == "face":                      # 512^2 face-like map, legacy-nearest lookup inside the kernel
-        lab = synth.synth_labels_face(b, 512, seed=seed).view(b, 512, 512)
-    elif kind == "blocks":                  # 8x8-pixel blocks at output resolution: boundaries inside every tile
-        lab = torch.randint(0, R, (b, (ho + 7) // 8, (wo + 7) // 8), generator=g).repeat_interleave(8, 1).repeat_interleave(8, 2)[:, :ho, :wo]
-    elif kind == "noise":                   # per-pixel random regions: every tile needs more variant rows than the kernel has
-        lab = torch.randint(0, R, (b, ho, wo), generator=g)
-    elif kind == "half-noise":              # left half noise (tiles overflow -> region-select kernel), right half two regions
-        lab = torch.randint(0, R, (b, ho, wo), generator=g)
-        lab[:, :, wo // 2:] = 3
-        lab[:, ho // 3:, wo // 2 + 5:] = R - 1
-    labels = lab.to(torch.uint8).contiguous().to(DEV)
-    kw = dict(labels=labels, num_regions=R, ncls=ncls, ostride=2 if up else 1,
-              in_scale=(torch.rand(b * R, cin, generator=g) + 0.5).to(DEV), out_scale=(torch.rand(b * R, cout, generator=g) + 0.5).to(DEV),
-              noise=torch.randn(b, 1, ho, wo, generator=g).to(DEV), noise_w=torch.tensor([0.2], device=DEV),
-              bias=(torch.randn(cout, generator=g) * 0.1).to(DEV), act=1)
-    return x, wt, kw
 
 
 @pytest.mark.parametrize("b,h,w,cin,cout,up,kind,R", [

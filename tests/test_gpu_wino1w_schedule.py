@@ -4,7 +4,7 @@ no K split):
   (a) against F.conv2d in fp64 with the bounds of test_winograd_f23_conv_vs_fp64 (3e-5 of the output scale; statistics 3e-5 of the
       scale for the mean, 1e-4 relative for 1 / sqrt(var + eps)),
   (b) bit-identical to the commit before the re-plan: SHA-256 of every output tensor's bytes == tests/golden/wino1w_parent_digests.json
-      (tools/wino1w_parent_digests.py wrote it from that commit's library: tools/build_prev_lib.sh + E4S_LIB_PATH).
+      (tools/parent_digests.py wrote it from that commit's library: tools/build_prev_lib.sh + E4S_LIB_PATH).
 Cases: both forms (InstanceNorm folded into the input transform + PReLU; output statistics); 320 tiles on 256 CUs (a block walks two tiles
 across a sample boundary, the statistics table switches parity); 16-wide maps of four tile rows (a tile is the left AND the right edge; top,
 inner and bottom rows); Cin = 128 = eight chunks, the fewest the policy sends to this kernel."""
@@ -26,10 +26,15 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "win
 # (8, 64, 16, 128 -> 512) would be 128 tiles, which the policy splits along K: nine samples keep it whole
 SHAPES = [(5, 64, 64, 256, 256), (5, 128, 128, 128, 128), (9, 64, 16, 128, 512)]
 MODES = ["in_prelu", "stats"]
+GOLDEN_ENV = {"E4S_WINO_1W": "1"}          # tools/parent_digests.py: the environment of the cases
 
 
 def case_id(shape, mode):
     return "x".join(str(s) for s in shape) + "_" + mode
+
+
+def golden_cases():
+    return {case_id(shape, mode): (shape, mode) for shape in SHAPES for mode in MODES}
 
 
 @functools.lru_cache(maxsize=None)

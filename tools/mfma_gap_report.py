@@ -35,13 +35,15 @@ def _build_module():
     return mod
 
 
-def compile_to_asm(src, extra):
+def compile_to_asm(src, extra, include=None):
+    """(flags, assembly text) of one .hip file; headers come from the file's own directory and from `include` (default: this tree's)."""
     b = _build_module()
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if not os.path.isfile(hipcc):
         hipcc = "hipcc"
     out = tempfile.NamedTemporaryFile(suffix=".s", delete=False).name
-    cmd = [hipcc, f"--offload-arch={b.ARCH}", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + b.CSRC]
+    cmd = [hipcc, f"--offload-arch={b.ARCH}", "-O3", "-std=c++17", "-I" + (include or os.path.join(ROOT, "include")),
+           "-I" + os.path.dirname(os.path.abspath(src))]
     cmd += b.PER_FILE_FLAGS.get(os.path.basename(src), []) + extra + ["--cuda-device-only", "-S", src, "-o", out]
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     if res.returncode != 0:
@@ -113,19 +115,26 @@ def kernels(text):
     return [(k, b) for k, b in out if any(kind(o) == "mfma" for _, bb in b for o in bb)]
 
 
-def spill_meta(text):
-    """symbol -> (sgpr spills, vgpr spills, private segment bytes) from the amdhsa.kernels metadata."""
+META_KEYS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
+             "group_segment_fixed_size")
+
+
+def kernel_meta(text):
+    """symbol -> {key: value} for META_KEYS, from the amdhsa.kernels metadata."""
     res = {}
-    for blk in re.split(r"\n\s+- \.agpr_count:", text)[1:]:
+    for blk in re.split(r"\n\s+- (?=\.agpr_count:)", text)[1:]:
         g = lambda key: (re.search(r"\." + key + r":\s+(\S+)", blk) or [None, "?"])[1]
-        res[g("name")] = (g("sgpr_spill_count"), g("vgpr_spill_count"), g("private_segment_fixed_size"))
+        res[g("name")] = {k: g(k) for k in META_KEYS}
     return res
 
 
-def report(sym, pretty, blocks, spills, show_gaps):
-    flat = [o for _, b in blocks for o in b]
-    idx = [i for i, o in enumerate(flat) if kind(o) == "mfma"]
-    scratch_between = sum(1 for o in flat[idx[0]:idx[-1]] if kind(o) == "scratch")
+def spill_meta(text):
+    """symbol -> (sgpr spills, vgpr spills, private segment bytes)"""
+    return {k: (m["sgpr_spill_count"], m["vgpr_spill_count"], m["private_segment_fixed_size"]) for k, m in kernel_meta(text).items()}
+
+
+def main_loop(blocks):
+    """(label, blocks, branches, v_mfma, [Counter of instruction kinds per gap]) of the kernel's main loop."""
     # the main loop: the innermost backward branch around the block with the most v_mfma
     nm = [sum(1 for o in b if kind(o) == "mfma") for _, b in blocks]
     main = nm.index(max(nm))
@@ -141,14 +150,19 @@ def report(sym, pretty, blocks, spills, show_gaps):
     ops = [o for _, b in blocks[lo:hi + 1] for o in b]
     nbr = sum(1 for o in ops if o.startswith(("s_branch", "s_cbranch")))
     pos = [i for i, o in enumerate(ops) if kind(o) == "mfma"]
-    gaps = []
-    for a, b in zip(pos, pos[1:]):
-        c = collections.Counter(kind(o) for o in ops[a + 1:b])
-        gaps.append(c)
+    gaps = [collections.Counter(kind(o) for o in ops[a + 1:b]) for a, b in zip(pos, pos[1:])]
+    return lab, hi - lo + 1, nbr, len(pos), gaps
+
+
+def report(sym, pretty, blocks, spills, show_gaps):
+    flat = [o for _, b in blocks for o in b]
+    idx = [i for i, o in enumerate(flat) if kind(o) == "mfma"]
+    scratch_between = sum(1 for o in flat[idx[0]:idx[-1]] if kind(o) == "scratch")
+    lab, nblk, nbr, nmfma, gaps = main_loop(blocks)
     print(f"== {pretty}")
     sg, vg, priv = spills.get(sym, ("?", "?", "?"))
     print(f"   spills: {vg} VGPR + {sg} SGPR, private segment {priv} B; scratch_ accesses between the first and the last v_mfma: {scratch_between}")
-    print(f"   main loop {lab}: {hi - lo + 1} block(s), {nbr} branch(es), {len(pos)} v_mfma, {len(gaps)} gaps")
+    print(f"   main loop {lab}: {nblk} block(s), {nbr} branch(es), {nmfma} v_mfma, {len(gaps)} gaps")
     if not gaps:
         return
     nv = [g["valu"] + g["cvt"] for g in gaps]

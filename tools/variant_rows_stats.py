@@ -2,7 +2,7 @@
 for every output pixel m of a tile and every 3x3 tap t, the halo pixel m + t needs a row scaled with region(m) whenever
 region(m) != region(m + t) (its own row carries its own region's style); rows are counted per distinct (halo pixel, region) pair.
 CPU only (numpy); prints the distribution per map size -- the numbers quoted in DESIGN.md 3.9 -- and the share of tiles that would
-overflow the kernel's 256 rows and fall back to the region-select kernel.
+overflow the kernel's 252 rows and fall back to the region-select kernel.
 
   python tools/variant_rows_stats.py [batch] [seed]"""
 import os
@@ -13,7 +13,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from e4s_amd import synth  # noqa: E402
 
-VMAX, T = 256, 16
+VMAX, T = 252, 16          # csrc/region_rows.h: VMAX = 18 stripes x 14 free slots, TW = TH = 16
 
 
 def nearest_down(lab, h):
