@@ -24,7 +24,7 @@
 //        the B stage is a straight 16-byte copy global -> VGPR -> LDS, double buffered.
 // The 144-byte row stride makes the ds_read_b128 fragment reads (lane -> row, lane half -> +16 B) conflict free, the
 // same argument as conv_mfma.hip.
-#include "common.h"
+#include "conv_launch.h"
 #include "few_tile_geom.h"
 #include <stdlib.h>
 
@@ -85,22 +85,6 @@ __device__ __forceinline__ void split_store(unsigned char* dst, const f32x8 v, c
     *reinterpret_cast<bf16x8*>(dst + lo) = l;
 }
 
-__global__ void splitk_epilogue_kernel(const e4s_conv_params p, const int ksplit, const int ycs, const int64_t hw,
-                                       const int64_t n4);
-
-// split-K policy shared by the plain and the region-select kernels: only when the tiles alone leave most CUs idle; every
-// split keeps >= 2 input-channel chunks
-inline void few_tiles_split(int64_t tiles, int nchunk, int& ksplit, int& cper) {
-    ksplit = 1;
-    cper = nchunk;
-    if (tiles > 128 || nchunk < 4) return;        // <= 128 tiles: two K halves fill the 256 CUs (the masked 32^2 layers ran on half the chip)
-    int want = (int)((256 + tiles - 1) / tiles);
-    if (want > nchunk / 2) want = nchunk / 2;
-    if (want < 2) return;
-    cper = (nchunk + want - 1) / want;
-    ksplit = (nchunk + cper - 1) / cper;
-}
-
 // E4S_REGION_PACK=0: small masked maps keep one image per tile (the A/B switch of the packed tiles; read once, like E4S_REGION_1W)
 inline bool region_pack_mode() {
     static const bool m = [] { const char* e = getenv("E4S_REGION_PACK"); return e ? atoi(e) != 0 : true; }();
@@ -110,17 +94,6 @@ inline bool region_pack_mode() {
 // masked launches on maps small enough that a 256-row tile holds several whole images (few_tile_geom.h): by map shape only
 inline bool region_packed(const e4s_conv_params& p) {
     return region_pack_mode() && p.labels && (p.ncls == 1 || p.ncls == 4) && e4s_few_tile::pack_geom(p.Ha, p.Wa).n_img >= 2;
-}
-
-// the ONE split rule of a masked launch: workspace size (both ws_floats entry points) and launcher ask here
-inline void region_split(const e4s_conv_params& p, int& ksplit, int& cper) {
-    if (region_packed(p)) {
-        const e4s_few_tile::PackGeom g = e4s_few_tile::pack_geom(p.Ha, p.Wa);
-        e4s_few_tile::pack_split((int64_t)e4s_few_tile::pack_tiles(g, p.B) * p.ncls * (p.Cout / 128), p.Cin / 32, ksplit, cper);
-        return;
-    }
-    const int64_t tiles = (int64_t)p.B * ((p.Ha + 15) / 16) * ((p.Wa + 15) / 16) * p.ncls * (p.Cout / 128);
-    few_tiles_split(tiles, p.Cin / 32, ksplit, cper);
 }
 
 struct TileId {          // one 16x16-pixel x BN-column output tile (x one K split: input-channel chunks [c_lo, c_hi))
@@ -942,7 +915,9 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_region_kernel(const e4s_conv
 
 template <int WN_, int SPL>
 int launch_region_v(const e4s_conv_params& p, const int* only_flagged, hipStream_t st) {
-    const bool pack = region_packed(p);
+    const e4s_masked_plan plan = e4s_plan_masked(p);
+    const bool pack = plan.path == 3;
+    const int ksplit = plan.ksplit, cper = plan.cper;
     if (pack && only_flagged) return (int)hipErrorInvalidValue;           // packed launches have no rows kernel in front and no flag table
     auto kern = pack ? conv_bf16x3_region_kernel<WN_, SPL, false, true>
                      : only_flagged ? conv_bf16x3_region_kernel<WN_, SPL, true> : conv_bf16x3_region_kernel<WN_, SPL, false>;
@@ -953,8 +928,6 @@ int launch_region_v(const e4s_conv_params& p, const int* only_flagged, hipStream
     // packed: tx_n = images per tile, one "tile per image" so that tt is the tile of the class
     const int tx_n = pack ? geo.n_img : (p.Wa + TW - 1) / TW, per_img = pack ? 1 : ((p.Ha + TH - 1) / TH) * tx_n;
     const int tiles_per_cls = pack ? e4s_few_tile::pack_tiles(geo, p.B) : p.B * per_img;
-    int ksplit, cper;
-    region_split(p, ksplit, cper);
     if (ksplit > 1 && !p.splitk_ws) return (int)hipErrorInvalidValue;
     const int64_t blocks = (int64_t)tiles_per_cls * p.ncls * ntn * ksplit;
     if (blocks <= 0) return 0;
@@ -963,15 +936,7 @@ int launch_region_v(const e4s_conv_params& p, const int* only_flagged, hipStream
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHR), SMEM_REGION, st, p, ntn, tx_n, per_img, tiles_per_cls,
                        ksplit, cper, only_flagged, (int)blocks);
     E4S_CHECK_LAUNCH();
-    if (ksplit > 1) {           // slabs already carry d[region]: the second stage adds them and applies noise / bias / act
-        e4s_conv_params q = p;
-        q.out_scale = nullptr;
-        const int64_t n4 = (int64_t)p.B * p.Ho * p.Wo * (p.Cout / 4);
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, q, ksplit, p.Cout,
-                           (int64_t)p.Ho * p.Wo, n4);
-        E4S_CHECK_LAUNCH();
-    }
-    return 0;
+    return ksplit > 1 ? e4s_splitk_epilogue(p, ksplit, false, st) : 0;      // slabs already carry d[region]
 }
 
 int launch_region(const e4s_conv_params& p, const int* only_flagged, hipStream_t st) {
@@ -1236,34 +1201,31 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_gather_kernel(const e4s_conv
     }
 }
 
-// K-split policy of the gather kernel (the workspace size and the launcher both ask here): only the 3x3 launches that leave three quarters
-// of the chip idle AND are deep enough that a split still runs >= 18 stages -- few_tiles_split on <= 64 tiles and >= 8 chunks.  (Cin < 256
-// stays whole: those launches keep their fused epilogue statistics, and their 36 / 72 stages are no longer than one split of the deep ones.)
-void gather_split(const e4s_conv_params& p, int& ksplit, int& cper) {
-    ksplit = 1;
-    cper = p.Cin / KC;
+// the gather kernel's launch: tiles, and the K split of split_policy.h's gather_split unless the output's channel stride is no multiple
+// of 4 (the second stage reads the slabs 16 bytes at a time)
+e4s_gather_plan gather_plan(const e4s_conv_params& p) {
+    e4s_gather_plan g;
     const int ycs = p.y_cstride ? p.y_cstride : p.Cout;
-    if (p.ntaps != 9 || p.Cin < 256 || p.Cin % KC || (ycs & 3)) return;
-    const int64_t tiles = (((int64_t)p.B * p.Ha * p.Wa + BM - 1) / BM) * ((p.Cout + BN - 1) / BN);
-    if (tiles <= 0 || tiles > 64) return;
-    few_tiles_split(tiles, p.Cin / KC, ksplit, cper);
+    g.ntn = (p.Cout + BN - 1) / BN;               // (Cout = 64: one half-used tile)
+    g.npix = (int64_t)p.B * p.Ha * p.Wa;
+    g.ntile = ((g.npix + BM - 1) / BM) * g.ntn;
+    e4s_split::gather_split((ycs & 3) ? 0 : g.ntile, p.Cin, p.ntaps, g.ksplit, g.cper);
+    g.slab_floats = g.ksplit > 1 ? g.ksplit * g.npix * ycs : 0;
+    return g;
 }
 
 int launch_gather(const e4s_conv_params& p, hipStream_t st) {
     auto kern = conv_bf16x3_gather_kernel;
     static std::atomic<uint64_t> smem_set{0};
     if (int e = e4s_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM_GATHER, smem_set)) return e;
-    const int ntn = (p.Cout + BN - 1) / BN;               // (Cout = 64: one half-used tile)
-    const int64_t npix = (int64_t)p.B * p.Ha * p.Wa;
-    if (npix <= 0) return 0;
-    if (npix * ntn >= (1ll << 31)) return (int)hipErrorInvalidValue;
-    const int64_t ntile = ((npix + BM - 1) / BM) * ntn;
-    int ksplit, cper;
-    gather_split(p, ksplit, cper);
-    if (ksplit > 1 && (!p.splitk_ws || p.stats_ws)) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(ntile * ksplit)), dim3(NTHR), SMEM_GATHER, st, p, ntn, (int)npix, (int)ntile, ksplit, cper);
+    const e4s_gather_plan g = gather_plan(p);
+    if (g.npix <= 0) return 0;
+    if (g.npix * g.ntn >= (1ll << 31)) return (int)hipErrorInvalidValue;
+    if (g.ksplit > 1 && (!p.splitk_ws || p.stats_ws)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(g.ntile * g.ksplit)), dim3(NTHR), SMEM_GATHER, st, p, g.ntn, (int)g.npix, (int)g.ntile, g.ksplit,
+                       g.cper);
     E4S_CHECK_LAUNCH();
-    return ksplit > 1 ? e4s_splitk_epilogue(p, ksplit, st) : 0;
+    return g.ksplit > 1 ? e4s_splitk_epilogue(p, g.ksplit, true, st) : 0;
 }
 
 // fp32 rows [rows][cin] -> split rows [rows][cin/32][hi x32 | lo x32] (bf16), same byte size
@@ -1310,58 +1272,46 @@ __global__ void splitk_epilogue_kernel(const e4s_conv_params p, const int ksplit
     *reinterpret_cast<f32x4*>(p.y + (size_t)pix * ycs + c) = v;
 }
 
-void plain_split(const e4s_conv_params& p, int ntn, int& ksplit, int& cper) {
-    const int64_t tiles = (int64_t)p.B * ((p.Ha + PTH - 1) / PTH) * ((p.Wa + TW - 1) / TW) * ntn;
-    few_tiles_split(tiles, p.Cin / KC, ksplit, cper);
-}
-
-int num_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (!cus[dev & 63]) {
-        hipDeviceProp_t prop;
-        cus[dev & 63] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                            ? prop.multiProcessorCount : 256;
-    }
-    return cus[dev & 63];
+// the plain kernel's launch: the column tile by Cout (the polyphase up-conv is ONE GEMM with 4 Cout columns), few_tiles_split over its tiles
+e4s_plain_plan plain_plan(const e4s_conv_params& p) {
+    e4s_plain_plan q;
+    const bool up = (p.ncls == 4);
+    q.config = up ? E4S_PLAIN_SHUF : p.Cout % 128 == 0 ? E4S_PLAIN_L16 : p.Cout % 64 == 0 ? E4S_PLAIN_M : E4S_PLAIN_S;
+#ifdef E4S_ABLATIONS
+    static const int k16 = [] { const char* e = getenv("E4S_PLAIN_K16"); return e ? atoi(e) : 1; }();
+    if (q.config == E4S_PLAIN_L16 && !k16) q.config = E4S_PLAIN_L;
+#endif
+    q.ntn = (up ? 4 * p.Cout : p.Cout) / (q.config == E4S_PLAIN_M ? 64 : q.config == E4S_PLAIN_S ? 32 : 128);
+    const int64_t tiles = (int64_t)p.B * ((p.Ha + PTH - 1) / PTH) * ((p.Wa + TW - 1) / TW) * q.ntn;
+    e4s_split::few_tiles_split(tiles, p.Cin / KC, q.ksplit, q.cper);
+    q.slab_floats = q.ksplit > 1 ? (int64_t)q.ksplit * p.B * p.Ho * p.Wo * (p.y_cstride ? p.y_cstride : p.Cout) : 0;
+    return q;
 }
 
 template <typename C, int XF, bool SHUF, int VAR = 0>
-int launch(const e4s_conv_params& p, hipStream_t st) {
+int launch(const e4s_conv_params& p, const e4s_plain_plan& plan, hipStream_t st) {
     auto kern = conv_bf16x3_kernel<C, XF, SHUF, VAR>;
     constexpr int SMEM = plain_smem<C, SHUF>();
     static_assert(SMEM <= 160 * 1024, "LDS budget");
     static std::atomic<uint64_t> smem_set{0};
     if (int e = e4s_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM, smem_set)) return e;
-    const int ngemm = SHUF ? 4 * p.Cout : p.Cout;
-    const int ntn = ngemm / C::BN;
+    const int ntn = plan.ntn, ksplit = plan.ksplit;
     const int tx_n = (p.Wa + TW - 1) / TW, per_img = ((p.Ha + PTH - 1) / PTH) * tx_n;
-    int ksplit, cper;
-    plain_split(p, ngemm / C::BN, ksplit, cper);             // policy in 32-channel chunks, whatever the kernel's chunk
-    cper *= 32 / C::KCH;
+    const int cper = plan.cper * (32 / C::KCH);              // policy in 32-channel chunks, whatever the kernel's chunk
     if (ksplit > 1 && !p.splitk_ws) return (int)hipErrorInvalidValue;
     const int64_t ntiles = (int64_t)p.B * per_img * ntn * ksplit;
     if (ntiles <= 0) return 0;
     if (ntiles >= (1ll << 31)) return (int)hipErrorInvalidValue;
-    const int grid = (int)(ntiles < num_cus() ? ntiles : num_cus());        // persistent: one block per CU
+    const int grid = (int)(ntiles < e4s_num_cus() ? ntiles : e4s_num_cus());        // persistent: one block per CU
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(PNTHR), SMEM, st, p, ntn, tx_n, per_img, (int)ntiles, ksplit, cper);
     E4S_CHECK_LAUNCH();
-    if (ksplit > 1) {
-        const int ycs = p.y_cstride ? p.y_cstride : p.Cout;
-        const int64_t npix = (int64_t)p.B * p.Ho * p.Wo;
-        const int64_t n4 = npix * (p.Cout / 4);
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, p, ksplit, ycs,
-                           (int64_t)p.Ho * p.Wo, n4);
-        E4S_CHECK_LAUNCH();
-    }
-    return 0;
+    return ksplit > 1 ? e4s_splitk_epilogue(p, ksplit, true, st) : 0;      // raw slabs: the second stage applies the demodulation
 }
 
 template <typename C, bool SHUF>
-int launch_xf(const e4s_conv_params& p, hipStream_t st) {
-    if (p.in_stats) return SHUF ? (int)hipErrorInvalidValue : launch<C, 2, false>(p, st);
-    return p.in_scale ? launch<C, 1, SHUF>(p, st) : launch<C, 0, SHUF>(p, st);
+int launch_xf(const e4s_conv_params& p, const e4s_plain_plan& plan, hipStream_t st) {
+    if (p.in_stats) return SHUF ? (int)hipErrorInvalidValue : launch<C, 2, false>(p, plan, st);
+    return p.in_scale ? launch<C, 1, SHUF>(p, plan, st) : launch<C, 0, SHUF>(p, plan, st);
 }
 
 }  // namespace
@@ -1370,7 +1320,6 @@ int launch_xf(const e4s_conv_params& p, hipStream_t st) {
 int e4s_launch_region_select(const e4s_conv_params& p, const int* only_flagged, hipStream_t st) {
     return launch_region(p, only_flagged, st);
 }
-void e4s_region_split_policy(const e4s_conv_params& p, int& ksplit, int& cper) { region_split(p, ksplit, cper); }
 bool e4s_region_packed(const e4s_conv_params& p) { return region_packed(p); }
 
 extern "C" int e4s_conv_bf16x3_f32(const e4s_conv_params* pp, void* stream) {
@@ -1401,37 +1350,36 @@ extern "C" int e4s_conv_bf16x3_f32(const e4s_conv_params* pp, void* stream) {
 #ifdef E4S_ABLATIONS      // profiling builds only (E4S_BUILD_ABLATIONS=1 python -m e4s_amd.build): tools/bench_abl.py
     static const int abl = [] { const char* e = getenv("E4S_BF16X3_ABL"); return e ? atoi(e) : 0; }();
     if (abl && !up && p.Cout % 128 == 0 && !p.in_stats && !p.in_scale) {
+        const e4s_plain_plan pl = plain_plan(p);
         switch (abl) {
-            case 1: return launch<CfgL, 0, false, 1>(p, st);
-            case 2: return launch<CfgL, 0, false, 2>(p, st);
-            case 3: return launch<CfgL, 0, false, 3>(p, st);
-            case 4: return launch<CfgL, 0, false, 4>(p, st);
-            case 5: return launch<CfgL, 0, false, 5>(p, st);
+            case 1: return launch<CfgL, 0, false, 1>(p, pl, st);
+            case 2: return launch<CfgL, 0, false, 2>(p, pl, st);
+            case 3: return launch<CfgL, 0, false, 3>(p, pl, st);
+            case 4: return launch<CfgL, 0, false, 4>(p, pl, st);
+            case 5: return launch<CfgL, 0, false, 5>(p, pl, st);
             default: break;
         }
     }
 #endif
     // one style per sample (or none): the persistent plain kernel.  The polyphase up-conv (ncls = 4) is ONE GEMM with
     // N = 4 Cout columns over the input grid + a pixel-shuffling epilogue.
-    if (up) {
-        if ((4 * p.Cout) % 128) return (int)hipErrorInvalidValue;
-        return launch_xf<CfgL, true>(p, st);
-    }
+    if (up && (4 * p.Cout) % 128) return (int)hipErrorInvalidValue;
+    const e4s_plain_plan plan = plain_plan(p);
+    switch (plan.config) {
+        case E4S_PLAIN_SHUF: return launch_xf<CfgL, true>(p, plan, st);
 #ifdef E4S_ABLATIONS
-    static const int k16 = [] { const char* e = getenv("E4S_PLAIN_K16"); return e ? atoi(e) : 1; }();
-    if (p.Cout % 128 == 0 && !k16) return launch_xf<CfgL, false>(p, st);
+        case E4S_PLAIN_L: return launch_xf<CfgL, false>(p, plan, st);
 #endif
-    if (p.Cout % 128 == 0) return launch_xf<CfgL16, false>(p, st);
-    if (p.Cout % 64 == 0) return launch_xf<CfgM, false>(p, st);
-    return launch_xf<CfgS, false>(p, st);
+        case E4S_PLAIN_L16: return launch_xf<CfgL16, false>(p, plan, st);
+        case E4S_PLAIN_M: return launch_xf<CfgM, false>(p, plan, st);
+        default: return launch_xf<CfgS, false>(p, plan, st);
+    }
 }
 
-// second stage of every split-K launch (also e4s_conv_mfma_f32's): slabs p.splitk_ws[k] (raw sums x demodulation) are added in
-// order, then noise / bias / activation
-int e4s_splitk_epilogue(const e4s_conv_params& p, int ksplit, hipStream_t st) {
+int e4s_splitk_epilogue(const e4s_conv_params& p, int ksplit, bool slabs_need_out_scale, hipStream_t st) {
     if (!p.splitk_ws || ksplit < 2 || p.Cout % 4) return (int)hipErrorInvalidValue;
     e4s_conv_params q = p;
-    q.out_scale = nullptr;
+    if (!slabs_need_out_scale) q.out_scale = nullptr;
     const int ycs = p.y_cstride ? p.y_cstride : p.Cout;
     const int64_t n4 = (int64_t)p.B * p.Ho * p.Wo * (p.Cout / 4);
     hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, q, ksplit, ycs,
@@ -1440,26 +1388,29 @@ int e4s_splitk_epilogue(const e4s_conv_params& p, int ksplit, hipStream_t st) {
     return 0;
 }
 
+int e4s_num_cus() {
+    static int cus[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    if (!cus[dev & 63]) {
+        hipDeviceProp_t prop;
+        cus[dev & 63] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+                            ? prop.multiProcessorCount : 256;
+    }
+    return cus[dev & 63];
+}
+
 extern "C" int64_t e4s_conv_bf16x3_ws_floats(const e4s_conv_params* pp) {
     const e4s_conv_params& p = *pp;
-    if (p.istride == 2 || p.ntaps == 1) {                                         // gather kernel: raw slabs of the deep few-tile 3x3 launches
-        int ksplit, cper;
-        gather_split(p, ksplit, cper);
-        return ksplit > 1 ? (int64_t)ksplit * p.B * p.Ha * p.Wa * (p.y_cstride ? p.y_cstride : p.Cout) : 0;
-    }
+    if (p.istride == 2 || p.ntaps == 1) return gather_plan(p).slab_floats;        // raw slabs of the deep few-tile 3x3 launches
     if (p.istride != 1 || p.ntaps != 9 || p.Cin % KC) return 0;
-    if (p.labels) {
-        int ksplit, cper;
-        region_split(p, ksplit, cper);
-        return ksplit > 1 ? (int64_t)ksplit * p.B * p.Ho * p.Wo * p.Cout : 0;
-    }
-    const bool up = (p.ncls == 4);
-    const int ngemm = up ? 4 * p.Cout : p.Cout;
-    const int bn = (up || p.Cout % 128 == 0) ? 128 : (p.Cout % 64 == 0 ? 64 : 32);
+    return p.labels ? e4s_plan_masked(p).slab_floats : plain_plan(p).slab_floats;
+}
+
+extern "C" int e4s_gather_ksplit(int64_t tiles, int cin, int ntaps) {
     int ksplit, cper;
-    plain_split(p, ngemm / bn, ksplit, cper);
-    if (ksplit <= 1) return 0;
-    return (int64_t)ksplit * p.B * p.Ho * p.Wo * (p.y_cstride ? p.y_cstride : p.Cout);
+    e4s_split::gather_split(tiles, cin, ntaps, ksplit, cper);
+    return ksplit;
 }
 
 extern "C" int e4s_split_bf16x2_f32(const float* w, void* out, int64_t rows, int cin, void* stream) {

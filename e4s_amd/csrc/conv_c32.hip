@@ -19,6 +19,7 @@
 // (row >> 1) & 7 instead of 144-byte padded rows (A 41 KB, B 36 KB), the output staging tile aliased over the halo buffer (one more
 // barrier per tile), four waves of 64 pixels (two accumulators; 6 fragment reads per 6 MFMAs instead of 4 per 3): 79 KB per block.
 // Arithmetic as conv_bf16x3.hip: three v_mfma_f32_32x32x16_bf16 per product on hi/lo-split fp32 operands, fp32 accumulate.
+#include "conv_launch.h"
 #include "mfma_rows.h"                                          // the swizzled [32 hi | 32 lo] row (swz, swz_halo and their bank analysis)
 #include <stdlib.h>
 
@@ -335,18 +336,6 @@ __global__ __launch_bounds__(256) void torgb_finish_kernel(const float* __restri
     }
 }
 
-int num_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (!cus[dev & 63]) {
-        hipDeviceProp_t prop;
-        cus[dev & 63] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                            ? prop.multiProcessorCount : 256;
-    }
-    return cus[dev & 63];
-}
-
 template <int XF, int RGB>
 int launch(const e4s_conv_params& p, const float* rgb_ws, float* rgb_partial, hipStream_t st) {
     auto kern = conv_c32_kernel<XF, RGB>;
@@ -356,7 +345,7 @@ int launch(const e4s_conv_params& p, const float* rgb_ws, float* rgb_partial, hi
     const int tx_n = (p.Wo + TW - 1) / TW, per_img = ((p.Ho + TH - 1) / TH) * tx_n;
     const int64_t ntiles = (int64_t)p.B * per_img * ntn;
     if (ntiles >= (1ll << 31)) return (int)hipErrorInvalidValue;
-    const int slots = 2 * num_cus();                                               // persistent, two co-resident blocks per CU
+    const int slots = 2 * e4s_num_cus();                                               // persistent, two co-resident blocks per CU
     const int grid = (int)(ntiles < slots ? ntiles : slots);
     int abl = 0;
 #ifdef E4S_ABLATIONS

@@ -22,7 +22,7 @@
 // the MFMAs).  LDS rows are 36 floats (144 B) so ds_read_b128 fragment reads are conflict free.
 // Style modulation s[g][ci] is applied to the B tile while it is staged (input-scaling form,
 // model.py:245-274); demodulation, noise, bias and leaky-ReLU live in the epilogue.
-#include "common.h"
+#include "conv_launch.h"
 #include <stdlib.h>
 
 namespace {
@@ -437,16 +437,20 @@ inline void f32_split(const e4s_conv_params& p, int64_t tiles_per_sample, int& k
     ksplit = 1;
     cper = nchunk;
     if (tiles_per_sample < 1 || nchunk < 4 || p.noise_per_channel || !p.splitk_ws) return;
+#ifdef E4S_ABLATIONS      // profiling builds only: the three switches of this rule
     static const int max_split = [] { const char* e = getenv("E4S_F32_MAX_SPLIT"); return e && atoi(e) > 0 ? atoi(e) : 8; }();
     static const int min_chunks = [] { const char* e = getenv("E4S_F32_MIN_CHUNKS"); return e && atoi(e) > 0 ? atoi(e) : 1; }();
+    static const int forced = [] { const char* e = getenv("E4S_F32_PLAIN_SPLIT"); return e ? atoi(e) : -1; }();
+#else
+    constexpr int max_split = 8, min_chunks = 1, forced = -1;
+#endif
     int want = nchunk / min_chunks;
     if (want > max_split) want = max_split;
     if (tiles_per_sample > 2) {
         // (plain contractions only: the styled / masked / tiled forms were never split above 2 tiles and their epilogues are not built for it)
-        // OPT-IN (p.split_hint, set by the frozen loss networks; env E4S_F32_PLAIN_SPLIT=1 forces it everywhere, =0 forbids it): the re-ordered sums
+        // OPT-IN (p.split_hint, set by the frozen loss networks; profiling builds: E4S_F32_PLAIN_SPLIT=1 forces it everywhere, =0 forbids it): the re-ordered sums
         // are as accurate as the unsplit ones (7e-7 of scale vs fp64), but through the TRAINED encoder's PReLU gates a re-ordering alone moved the
         // worst weight-gradient tensor of the fp64 gradient test from 1.7e-3 to 3.1e-3 relative L2 (gate flips on 512-pixel maps)
-        static const int forced = [] { const char* e = getenv("E4S_F32_PLAIN_SPLIT"); return e ? atoi(e) : -1; }();
         const bool on = forced >= 0 ? forced != 0 : p.split_hint != 0;
         if (!on || p.labels || p.in_scale || p.out_scale || p.noise || p.tiles || p.in_stats || p.ncls != 1) return;
         // Round 6: maps of a few dozen tiles too (the batch-1 encoder's stride-2 convs: 32 tiles x 4 column tiles = 128 blocks per sample, one
@@ -492,7 +496,7 @@ int launch(const e4s_conv_params& p, hipStream_t st) {
     f32_split(p, tiles_per_sample<BM, SPATIAL>(p) / p.ncls, ksplit, cper);
     hipLaunchKernelGGL(kern, dim3(mtiles * ntn, ksplit), dim3(NTHR), L::BYTES, st, p, ntn, tiles_per_cls, ksplit, cper);
     E4S_CHECK_LAUNCH();
-    if (ksplit > 1) return e4s_splitk_epilogue(p, ksplit, st);     // slabs already carry the demodulation
+    if (ksplit > 1) return e4s_splitk_epilogue(p, ksplit, false, st);     // slabs already carry the demodulation
     return 0;
 }
 

@@ -19,15 +19,10 @@
 // [tap][Cin/16][Cout][16 hi | 16 lo] layout of e4s_split16_bf16x2_f32: a stage's B tile is three contiguous 8 KB runs.
 // Block = 512 threads = 4 x 2 waves of 64 x 64, tile 256 pixels x 128 output channels, one block per CU (128 KB of LDS).
 // What a tile IS -- row layout, tables, analysis steps 2-4, staging items -- is region_rows.h, shared with conv_region1w.hip.
-#include "common.h"
+#include "conv_launch.h"
+#include "few_tile_geom.h"
 #include "region_rows.h"
 #include <stdlib.h>
-
-int e4s_launch_region_select(const e4s_conv_params& p, const int* only_flagged, hipStream_t st);      // conv_bf16x3.hip
-void e4s_region_split_policy(const e4s_conv_params& p, int& ksplit, int& cper);                       // conv_bf16x3.hip
-bool e4s_region_packed(const e4s_conv_params& p);                                                     // conv_bf16x3.hip
-bool e4s_region_rows1w_ok(const e4s_conv_params& p);                                                  // conv_region1w.hip
-int e4s_launch_region_rows1w(const e4s_conv_params& p, const void* w16, int* flags, hipStream_t st, int layout);  // conv_region1w.hip
 
 namespace {
 
@@ -358,36 +353,46 @@ static bool region_rows_ok(const e4s_conv_params& p) {
            (int64_t)p.Hi * p.Wi * p.Cin < (1ll << 31) && (int64_t)p.B * p.Ho * p.Wo < (1ll << 31);
 }
 
-extern "C" int64_t e4s_conv_region_ws_floats(const e4s_conv_params* pp) {
-    const e4s_conv_params& p = *pp;
-    if (!region_rows_ok(p)) return 0;
-    int ksplit, cper;
-    e4s_region_split_policy(p, ksplit, cper);
-    const int64_t tiles = (int64_t)p.B * ((p.Ha + TH - 1) / TH) * ((p.Wa + TW - 1) / TW) * p.ncls;
-    return (ksplit > 1 ? (int64_t)ksplit * p.B * p.Ho * p.Wo * p.Cout : 0) + tiles;        // [split-K slabs][tile flags]
-}
-
 static int region_1w_mode() {
     static const int m = [] { const char* e = getenv("E4S_REGION_1W"); return e ? atoi(e) : 1; }();
     return m;
 }
 
-extern "C" int e4s_conv_region_path(const e4s_conv_params* pp) {
-    if (!pp || !region_rows_ok(*pp)) return 0;
-    if (e4s_region_packed(*pp)) return 3;          // small maps: several whole images per tile of the region-select kernel
-    int ksplit, cper;
-    e4s_region_split_policy(*pp, ksplit, cper);
-    return (region_1w_mode() && ksplit == 1 && e4s_region_rows1w_ok(*pp)) ? 2 : 1;
+// THE launch plan of a masked conv, for both entry points (this file's and e4s_conv_bf16x3_f32's `labels` branch): small maps pack several
+// whole images per tile (few_tile_geom.h) and split by pack_split; the others have one tile per image and 16x16 patch and split by
+// few_tiles_split; launches that fill the chip without a split and have >= 256 output channels go to the one-wave-per-SIMD kernel
+// (256 x 256 tiles, conv_region1w.hip; E4S_REGION_1W=0 keeps this file's kernel: the A/B switch of tools/bench_region.py)
+e4s_masked_plan e4s_plan_masked(const e4s_conv_params& p) {
+    e4s_masked_plan m;
+    const int64_t ctiles = (int64_t)p.ncls * (p.Cout / BN);
+    m.flag_ints = (int64_t)p.B * ((p.Ha + TH - 1) / TH) * ((p.Wa + TW - 1) / TW) * p.ncls;
+    if (e4s_region_packed(p)) {
+        m.path = 3;
+        e4s_split::pack_split(e4s_few_tile::pack_tiles(e4s_few_tile::pack_geom(p.Ha, p.Wa), p.B) * ctiles, p.Cin / 32, m.ksplit, m.cper);
+    } else {
+        e4s_split::few_tiles_split(m.flag_ints * (p.Cout / BN), p.Cin / 32, m.ksplit, m.cper);
+        m.path = (region_1w_mode() && m.ksplit == 1 && e4s_region_rows1w_ok(p)) ? 2 : 1;
+    }
+    m.slab_floats = m.ksplit > 1 ? (int64_t)m.ksplit * p.B * p.Ho * p.Wo * p.Cout : 0;
+    return m;
 }
+
+extern "C" int64_t e4s_conv_region_ws_floats(const e4s_conv_params* pp) {
+    if (!region_rows_ok(*pp)) return 0;
+    const e4s_masked_plan m = e4s_plan_masked(*pp);
+    return m.slab_floats + m.flag_ints;        // [split-K slabs][tile flags]
+}
+
+extern "C" int e4s_conv_region_path(const e4s_conv_params* pp) { return pp && region_rows_ok(*pp) ? e4s_plan_masked(*pp).path : 0; }
 
 extern "C" int e4s_conv_region_bf16x3_f32(const e4s_conv_params* pp, const void* w16, void* stream) {
     const e4s_conv_params& p = *pp;
     if (!region_rows_ok(p)) return (int)hipErrorInvalidValue;
     hipStream_t st = as_stream(stream);
-    int ksplit, cper;
-    e4s_region_split_policy(p, ksplit, cper);
-    // small maps (4^2, 8^2: few_tile_geom.h) go straight to the region-select kernel's packed tiles: no rows kernel, no overflow scan
-    if (!w16 || e4s_region_packed(p)) return e4s_launch_region_select(p, nullptr, st);
+    const e4s_masked_plan m = e4s_plan_masked(p);
+    const int ksplit = m.ksplit;
+    // small maps (4^2, 8^2) go straight to the region-select kernel's packed tiles: no rows kernel, no overflow scan
+    if (!w16 || m.path == 3) return e4s_launch_region_select(p, nullptr, st);
     if (!p.splitk_ws) return (int)hipErrorInvalidValue;
     auto kern = conv_region_rows_kernel;
     static std::atomic<uint64_t> smem_set{0};
@@ -398,16 +403,13 @@ extern "C" int e4s_conv_region_bf16x3_f32(const e4s_conv_params* pp, const void*
     const int64_t blocks = (int64_t)tiles_per_cls * p.ncls * ntn * ksplit;
     if (blocks <= 0) return 0;
     if (blocks >= (1ll << 31)) return (int)hipErrorInvalidValue;
-    int* flags = reinterpret_cast<int*>(p.splitk_ws + (ksplit > 1 ? (size_t)ksplit * p.B * p.Ho * p.Wo * p.Cout : 0));
-    // launches that fill the chip without a K split and have >= 256 output channels: the one-wave-per-SIMD kernel (256 x 256 tiles,
-    // conv_region1w.hip; E4S_REGION_1W=0 keeps this file's kernel: the A/B switch of tools/bench_region.py)
-    const int use_1w = region_1w_mode();
-    if (use_1w && ksplit == 1 && e4s_region_rows1w_ok(p)) {
-        if (int e = e4s_launch_region_rows1w(p, w16, flags, st, use_1w)) return e;
+    int* flags = reinterpret_cast<int*>(p.splitk_ws + m.slab_floats);
+    if (m.path == 2) {
+        if (int e = e4s_launch_region_rows1w(p, w16, flags, st, region_1w_mode())) return e;
         return e4s_launch_region_select(p, flags, st);
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NTHR), SMEM, st, p, reinterpret_cast<const unsigned char*>(w16), flags,
-                       ntn, tx_n, per_img, tiles_per_cls, ksplit, cper * (32 / KC));
+                       ntn, tx_n, per_img, tiles_per_cls, ksplit, m.cper * (32 / KC));
     E4S_CHECK_LAUNCH();
     // tiles with > VMAX variant rows (flag table written by the launch above) on the region-select kernel, same K split and slabs;
     // that launcher also runs the second stage of a split launch

@@ -27,7 +27,7 @@
 // region_rows.h, shared with conv_region.hip; the tile decode, the label lookup, analysis steps 2-3 and the staging items are written out here, in the
 // words of that header (measured: DESIGN 3.9 -- with them in shared functions this kernel's prologue changes and the polyphase 512 -> 512 launch loses 0.5-0.8 %); the weight image ([tap][Cin/16][Cout][16 hi | 16 lo], e4s_split16_bf16x2_f32) and the flag table for tiles with > VMAX
 // variant rows are that file's.
-#include "common.h"
+#include "conv_launch.h"
 #include "region_rows.h"
 #include <stdlib.h>
 

@@ -358,8 +358,12 @@ template <int IS>
 constexpr int wg_smem() { return (WgTile<IS>::NA * BC + WgTile<IS>::NH * BC + MAXR * BC) * 4 + WgTile<IS>::NA * 4; }
 
 static bool wg_bf16x3(const e4s_conv_wgrad_params& p) {            // E4S_WGRAD_BF16X3 (A/B switch): 0 = the exact-fp32 kernel everywhere, 2 = only without a region map
+#ifdef E4S_ABLATIONS      // profiling builds only
     static const int on = [] { const char* e = getenv("E4S_WGRAD_BF16X3"); return e ? atoi(e) : 1; }();
     static const int min_masked = [] { const char* e = getenv("E4S_WGRAD_MASKED_MIN_ANCHORS"); return e ? atoi(e) : 0; }();
+#else
+    constexpr int on = 1, min_masked = 0;
+#endif
     if (!on || p.ntaps != 9) return false;
     if ((int64_t)p.Ho * p.Wo * p.Cout >= (1ll << 31) || (int64_t)p.Hi * p.Wi * p.Cin >= (1ll << 31)) return false;      // 32-bit element offsets per sample
     if (p.istride == 2) return !p.labels && on != 3;                        // (3: stride 1 only, the A/B switch of the stride-2 form)
@@ -370,7 +374,11 @@ int wg_nsplit(const e4s_conv_wgrad_params& p) {
     if (wg_bf16x3(p)) {
         // two blocks per CU, but at least 4 anchor tiles (K = 256) per block where the layer has them: a block's 147 KB slab (write, read by the
         // reduction) and its 36 wide stores per lane cost about what two tiles of MFMAs do
+#ifdef E4S_ABLATIONS
         static const int target = [] { const char* e = getenv("E4S_WGRAD_BLOCKS"); return e && atoi(e) > 0 ? atoi(e) : 512; }();
+#else
+        constexpr int target = 512;
+#endif
         const int th = p.istride == 2 ? WB<2>::TH : WB<1>::TH;
         const int ntiles = p.B * ((p.Ha + th - 1) / th) * ((p.Wa + WB_TW - 1) / WB_TW);
         const int ctiles = ((p.Cout + BC - 1) / BC) * ((p.Cin + BC - 1) / BC);

@@ -30,12 +30,11 @@
 // the three differences], 16 values split to hi / lo, eight 8-byte LDS stores.  The 576 items of chunk c+1 are spread over the three
 // stages of chunk c, three waves per stage, rotating through the eight.
 // Persistent (grid = min(tiles, CUs); the pipeline runs through the tile boundary) and split-K for launches of <= 128 tiles.
-#include "common.h"
+#include "conv_launch.h"
 #include "rows64.h"
 #include <stdlib.h>
 #include <type_traits>
 
-int e4s_launch_wino1w(const e4s_conv_params& p, int ntn, int tx_n, int per_img, int ntiles, int grid, hipStream_t st);      // conv_wino1w.hip
 
 namespace {
 
@@ -666,41 +665,20 @@ __global__ __launch_bounds__(NTHR) void conv_wino_kernel(const e4s_conv_params p
     }
 }
 
-int wino_num_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (!cus[dev & 63]) {
-        hipDeviceProp_t prop;
-        cus[dev & 63] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        if (const char* g = getenv("E4S_WINO_GRID")) {          // testing aid: fewer blocks, so that small shapes walk several tiles per block
-            const int v = atoi(g);
-            if (v > 0) cus[dev & 63] = v;
-        }
-    }
-    return cus[dev & 63];
-}
-
-// split-K policy (the plain kernel's, on 16-channel chunks): only when the tiles alone leave most CUs idle; every split keeps >= 2 chunks
-void wino_split(const e4s_conv_params& p, int64_t tiles, int& ksplit, int& cper) {
-    const int nchunk = p.Cin / KC;
-    ksplit = 1;
-    cper = nchunk;
-    if (tiles > 128 || nchunk < 4) return;
-    int want = (int)((256 + tiles - 1) / tiles);
-    if (want > nchunk / 2) want = nchunk / 2;
-    if (want < 2) return;
-    const int c = (nchunk + want - 1) / want, k = (nchunk + c - 1) / c;
-    if (k < 2 || nchunk - (k - 1) * c < 2) return;
-    ksplit = k;
-    cper = c;
-}
-
 bool wino_covers(const e4s_conv_params& p) {
     return p.istride == 1 && p.ostride == 1 && p.ntaps == 9 && p.ncls == 1 && !p.labels && !p.rows && !p.in_scale && !p.out_scale &&
            !p.noise && p.y_cstride == 0 && p.Hi == p.Ho && p.Wi == p.Wo && p.Ha == p.Ho && p.Wa == p.Wo && p.Hi % TH == 0 &&
            p.Wi % TW == 0 && p.Cin % KC == 0 && p.Cin >= 2 * KC && p.Cout % BN == 0 && p.B > 0 &&
            (p.stats_ws == nullptr || p.stats_slots == (p.Hi / TH) * (p.Wi / TW));
+}
+
+// the launch of a shape wino_covers() accepted: one 16x16-pixel x 128-column tile per block, few_tiles_split_guarded over 16-channel chunks
+e4s_wino_plan wino_plan(const e4s_conv_params& p) {
+    e4s_wino_plan w;
+    w.tx_n = p.Wi / TW, w.per_img = (p.Hi / TH) * w.tx_n, w.ntn = p.Cout / BN;
+    e4s_split::few_tiles_split_guarded((int64_t)p.B * w.per_img * w.ntn, p.Cin / KC, w.ksplit, w.cper);
+    w.slab_floats = w.ksplit > 1 ? (int64_t)w.ksplit * p.B * p.Ho * p.Wo * p.Cout : 0;
+    return w;
 }
 
 }  // namespace
@@ -723,11 +701,7 @@ extern "C" int e4s_conv_wino_covers(const e4s_conv_params* p) { return p && wino
 
 /* floats of p->splitk_ws the launch needs (0: no split-K; then stats_ws is honoured) */
 extern "C" int64_t e4s_conv_wino_ws_floats(const e4s_conv_params* pp) {
-    if (!pp || !wino_covers(*pp)) return 0;
-    const e4s_conv_params& p = *pp;
-    int ksplit, cper;
-    wino_split(p, (int64_t)p.B * (p.Hi / TH) * (p.Wi / TW) * (p.Cout / BN), ksplit, cper);
-    return ksplit > 1 ? (int64_t)ksplit * p.B * p.Ho * p.Wo * p.Cout : 0;
+    return pp && wino_covers(*pp) ? wino_plan(*pp).slab_floats : 0;
 }
 
 extern "C" int e4s_conv_wino_bf16x3_f32(const e4s_conv_params* pp, void* stream) {
@@ -735,15 +709,18 @@ extern "C" int e4s_conv_wino_bf16x3_f32(const e4s_conv_params* pp, void* stream)
     const e4s_conv_params& p = *pp;
     if (!p.x || !p.w || !p.y || !wino_covers(p)) return (int)hipErrorInvalidValue;
     if (p.act == 2 && !p.slope) return (int)hipErrorInvalidValue;
-    const int tx_n = p.Wi / TW, per_img = (p.Hi / TH) * tx_n, ntn = p.Cout / BN;
-    int ksplit, cper;
-    wino_split(p, (int64_t)p.B * per_img * ntn, ksplit, cper);
+    const e4s_wino_plan w = wino_plan(p);
+    const int tx_n = w.tx_n, per_img = w.per_img, ntn = w.ntn, ksplit = w.ksplit, cper = w.cper;
     if (ksplit > 1 && !p.splitk_ws) return (int)hipErrorInvalidValue;
     const int64_t tiles = (int64_t)p.B * per_img * ntn * ksplit;
     if (tiles > 0x7fffffff) return (int)hipErrorInvalidValue;
     static std::atomic<uint64_t> m0{0}, m2{0};
     int e;
-    const int ncu = wino_num_cus();
+    int ncu = e4s_num_cus();
+#ifdef E4S_ABLATIONS
+    if (const char* g = getenv("E4S_WINO_GRID"))          // testing aid: fewer blocks, so that small shapes walk several tiles per block
+        if (atoi(g) > 0) ncu = atoi(g);
+#endif
     const int64_t grid = tiles < ncu ? tiles : ncu;                               // persistent: one block per CU
 #ifdef E4S_ABLATIONS
     {
@@ -798,6 +775,6 @@ extern "C" int e4s_conv_wino_bf16x3_f32(const e4s_conv_params* pp, void* stream)
                            (int)tiles, ksplit, cper);
     }
     E4S_CHECK_LAUNCH();
-    if (ksplit > 1) return e4s_splitk_epilogue(p, ksplit, as_stream(stream));      // ordered slab sum + bias / activation (conv_bf16x3.hip)
+    if (ksplit > 1) return e4s_splitk_epilogue(p, ksplit, false, as_stream(stream));      // ordered slab sum + bias / activation (conv_bf16x3.hip)
     return 0;
 }

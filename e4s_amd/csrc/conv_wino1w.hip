@@ -24,7 +24,7 @@
 //     tools/mfma_gap_report.py prints what the compiler made of it (profiles/r10_wino1w_gaps.txt: the largest gap went from 32 VALU to 6,
 //     the modelled overrun from 17 % to 0.5 %; measured -9 ... -12 % per launch in the step).
 // Split-K launches (<= 128 tiles) and short-K layers stay on conv_wino_kernel.
-#include "common.h"
+#include "conv_launch.h"
 #include "rows64.h"
 #include <stdlib.h>
 #include <type_traits>

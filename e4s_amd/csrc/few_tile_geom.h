@@ -1,4 +1,4 @@
-// Geometry of the PACKED small-map tiles of conv_bf16x3_region_kernel (conv_bf16x3.hip) and the K-split rule of those launches.
+// Geometry of the PACKED small-map tiles of conv_bf16x3_region_kernel (conv_bf16x3.hip); the K-split rule of those launches is split_policy.h's pack_split.
 //
 // The region-select kernel cuts 256-row x 128-column GEMM tiles whose rows are the pixels of ONE 16x16 patch of ONE image: a 4x4 map fills 16
 // of the 256 rows, an 8x8 map 64.  A packed tile holds n_img WHOLE images of such a map instead:
@@ -9,6 +9,7 @@
 // n_img = min(324 / ((Ha+2)(Wa+2)), 256 / (Ha Wa)); a map is eligible when n_img >= 2 (9 images at 4x4, 3 at 8x8; 16x16 is not).
 // Plain C++ with no device code, so the host tests compile it as it is.
 #pragma once
+#include "split_policy.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define E4S_FT_HD __host__ __device__ inline
@@ -20,7 +21,8 @@ namespace e4s_few_tile {
 
 constexpr int kRows = 256;        // GEMM rows of a tile
 constexpr int kHalo = 324;        // halo rows of a tile: (16 + 2)^2
-constexpr int kBlocks = 256;      // blocks a launch should reach (one per CU)
+using e4s_split::kBlocks;          // blocks a launch should reach, and the K split of a packed launch: split_policy.h
+using e4s_split::pack_split;
 
 struct PackGeom {
     int ha, wa;        // map size
@@ -81,19 +83,6 @@ E4S_FT_HD PackSlot pack_slot(const PackGeom& g, int t, int h, int batch) {
     const int image = t * g.n_img + s.j;
     s.image = (s.j < g.n_img && image < batch) ? image : -1;
     return s;
-}
-
-// K split of a packed launch of `tiles` blocks (all classes and column tiles) over nchunk 32-channel chunks: as many splits as still fit ONE
-// round of kBlocks blocks (one block per CU: a launch just past 256 blocks would run two rounds), down to one chunk per block
-E4S_FT_HD void pack_split(long long tiles, int nchunk, int& ksplit, int& cper) {
-    ksplit = 1;
-    cper = nchunk;
-    if (tiles < 1 || nchunk < 2) return;
-    long long want = kBlocks / tiles;
-    if (want > nchunk) want = nchunk;
-    if (want < 2) return;
-    cper = (nchunk + (int)want - 1) / (int)want;
-    ksplit = (nchunk + cper - 1) / cper;
 }
 
 }  // namespace e4s_few_tile

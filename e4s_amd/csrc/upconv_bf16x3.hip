@@ -29,7 +29,7 @@
 //     multiply-adds per output instead of 16, 0.77 -> 0.71 / 0.60 -> 0.57 ms.
 // Weights arrive pre-packed and pre-split by e4s_subpixel_weights_f32: [Cin/32][Cout/32][9 blocks][32 co][32 hi | 32 lo bf16]; a stage
 // takes one 16-channel half of a row.
-#include "common.h"
+#include "conv_launch.h"
 #include <stdlib.h>
 
 namespace {
@@ -450,18 +450,6 @@ __global__ void subpixel_weights_kernel(const float* __restrict__ w, unsigned sh
     *reinterpret_cast<bf16x8*>(d + 32) = l;
 }
 
-int num_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (!cus[dev & 63]) {
-        hipDeviceProp_t prop;
-        cus[dev & 63] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                            ? prop.multiProcessorCount : 256;
-    }
-    return cus[dev & 63];
-}
-
 }  // namespace
 
 // out: (Cin/32) * (Cout/32) * 9 * 32 * 64 bf16 = 9 * Cout * Cin * 4 bytes (an opaque buffer only e4s_upconv_bf16x3_f32 reads)
@@ -491,7 +479,7 @@ extern "C" int e4s_upconv_bf16x3_f32(const e4s_conv_params* pp, const float* k4,
     const int tx_n = (p.Wo + OW - 1) / OW, per_img = ((p.Ho + OH - 1) / OH) * tx_n;
     const int64_t ntiles = (int64_t)p.B * per_img * ntn;
     if (ntiles >= (1ll << 31)) return (int)hipErrorInvalidValue;
-    const int slots = 2 * num_cus();                    // two co-resident blocks per CU
+    const int slots = 2 * e4s_num_cus();                    // two co-resident blocks per CU
     const int grid = (int)(ntiles < slots ? ntiles : slots);
     int abl = 0;
 #ifdef E4S_ABLATIONS

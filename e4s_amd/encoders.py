@@ -58,17 +58,22 @@ def _conv3x3(x, conv, cout, in_stats=None, want_stats=False, **kw):
     return K.conv_mfma(x, w, cout, want_stats=want_stats, **kw)
 
 
+def strided_bf16x3(b, h, w, cin, cout, stride, ntaps):
+    """Policy of K.PRECISION for the unit's strided convs: split-bf16 where the gather kernel covers the width and the launch has enough
+    256-pixel tiles (x the K splits of deep 3x3 launches: K.gather_split), exact fp32 otherwise."""
+    covered = cout % 128 == 0 or cout == 64                      # (64: one half-used 128-column tile of the gather kernel)
+    tiles = (b * (h // stride) * (w // stride) + 255) // 256 * ((cout + 127) // 128 if covered else 0)
+    filled = K.fills_chip(tiles, cin // 32, K.gather_split(tiles, cin, ntaps))
+    return K.PRECISION != "f32" and covered and (K.PRECISION == "bf16x3" or filled)
+
+
 def _conv_strided(x, conv, cout, stride, ntaps, want_stats=False, se=None, **kw):
     """The unit's stride-2 3x3 conv / 1x1 shortcut conv (helpers.py:125-137): per-tap gather kernels -- split-bf16 where
     K.PRECISION asks for it and the launch has enough 256-pixel tiles (x K splits), exact fp32 otherwise.  kw: epilogue (bias / act /
     alpha / gain) passed through to conv_mfma (the face parser's folded BatchNorm + ReLU)."""
     w = _pack3x3(conv)
-    b, h, wd, _ = x.shape
-    covered = cout % 128 == 0 or cout == 64                      # (64: one half-used 128-column tile of the gather kernel)
-    tiles = (b * (h // stride) * (wd // stride) + 255) // 256 * ((cout + 127) // 128 if covered else 0)
-    # few tiles: the gather kernel splits deep 3x3 launches over the input channels (csrc gather_split), K.want_bf16x3's form
-    filled = tiles >= K.BF16X3_MIN_BLOCKS or tiles * K.gather_split(tiles, x.shape[3], ntaps) >= 64
-    if K.PRECISION != "f32" and covered and (K.PRECISION == "bf16x3" or filled):
+    b, h, wd, cin = x.shape
+    if strided_bf16x3(b, h, wd, cin, cout, stride, ntaps):
         if getattr(conv, "_e4s_split", None) is None or conv._e4s_split[0] != conv._e4s_pack[0]:
             conv._e4s_split = (conv._e4s_pack[0], K.split_bf16x2(w))
         return K.conv_mfma(x, w, cout, istride=stride, ntaps=ntaps, w_split=conv._e4s_split[1], want_stats=want_stats, se=se, **kw)

@@ -436,6 +436,19 @@ def bf16x3_eligible(cin, cout, *, istride=1, ostride=1, ntaps=9, ncls=1, masked=
             and (ncls, ostride) in ((1, 1), (4, 2)))
 
 
+def fills_chip(tiles, nchunk, ksplit=None):
+    """Policy ESTIMATE: does a split-bf16 launch of `tiles` tiles over `nchunk` input-channel chunks keep the chip busy -- >= BF16X3_MIN_BLOCKS
+    tiles, or >= 64 blocks once the library splits K?  The library's rules are csrc/split_policy.h; only the gather rule is asked there
+    (ksplit = gather_split(...)).  Otherwise the splits are taken as the number few_tiles_split WANTS, min(nchunk // 2, ceil(256 / tiles)),
+    which overcounts: the rule rounds it down to ceil(nchunk / ceil(nchunk / want)) parts, the Winograd form refuses a split whose last
+    part is one chunk, and neither splits above 128 tiles (DESIGN section 6 lists the shapes where the answers differ)."""
+    if tiles >= BF16X3_MIN_BLOCKS:
+        return True
+    if ksplit is None:
+        ksplit = min(nchunk // 2, -(-256 // tiles)) if nchunk >= 4 else 1
+    return tiles * max(ksplit, 1) >= 64
+
+
 def want_bf16x3(b, h, w, cin, cout, ncls=1, masked=False):
     """Policy of PRECISION for a natural-order 3x3 conv (ncls = 4: polyphase up-conv) on [b,h,w,cin] -> cout."""
     if PRECISION == "f32" or not bf16x3_eligible(cin, cout, ncls=ncls, ostride=2 if ncls == 4 else 1, masked=masked):
@@ -446,25 +459,13 @@ def want_bf16x3(b, h, w, cin, cout, ncls=1, masked=False):
     n = 4 * cout if (ncls == 4 and not masked) else cout
     bn = 128 if n % 128 == 0 else 64 if n % 64 == 0 else 32
     tiles = b * ((h + 15) // 16) * ((w + 15) // 16) * (n // bn) * (ncls if masked else 1)
-    if tiles >= BF16X3_MIN_BLOCKS:
-        return True       # (at exactly 128 tiles the kernels also split K two ways: csrc few_tiles_split)
-    # few tiles (batch-1 latency runs): the kernels split the input channels over blocks (csrc: few_tiles_split)
-    nchunk = cin // 32
-    split = min(nchunk // 2, -(-256 // tiles)) if nchunk >= 4 else 1
-    return tiles * max(split, 1) >= 64
+    return fills_chip(tiles, cin // 32)       # few tiles (batch-1 latency runs): the kernels split the input channels over blocks
 
 
 def gather_split(tiles, cin, ntaps):
-    """K splits of a strided (gather-kernel) split-bf16 launch of `tiles` 256-pixel x 128-column tiles (csrc/conv_bf16x3.hip gather_split):
-    3x3, <= 64 tiles, Cin >= 256; every split keeps >= 2 chunks of 32 input channels."""
-    if ntaps != 9 or tiles < 1 or tiles > 64 or cin < 256 or cin % 32:
-        return 1
-    nchunk = cin // 32
-    want = min(nchunk // 2, -(-256 // tiles))
-    if want < 2:
-        return 1
-    cper = -(-nchunk // want)
-    return -(-nchunk // cper)
+    """K splits of a strided (gather-kernel) split-bf16 launch of `tiles` 256-pixel x 128-column tiles: the library's own rule
+    (e4s_gather_ksplit: 3x3, <= 64 tiles, Cin >= 256)."""
+    return lib.load().e4s_gather_ksplit(tiles, cin, ntaps)
 
 
 def split_bf16x2(w, out=None):
@@ -496,15 +497,15 @@ def split16_bf16x2(w, out=None):
     return out
 
 
-REGION_1W = os.environ.get("E4S_REGION_1W", "1") != "0"        # mirrors the library's switch (csrc/conv_region.hip)
-REGION_PACK = os.environ.get("E4S_REGION_PACK", "1") != "0"    # mirrors the library's switch (csrc/conv_bf16x3.hip): packed small-map tiles
+REGION_1W = os.environ.get("E4S_REGION_1W", "1") != "0"        # the library reads the same variable (csrc/conv_region.hip e4s_plan_masked)
+REGION_PACK = os.environ.get("E4S_REGION_PACK", "1") != "0"    # the library reads the same variable (csrc/conv_bf16x3.hip): packed small-map tiles
 LAST_REGION_PATH = 0           # which kernel the last masked launch took (e4s_conv_region_path): 1 8-wave rows kernel, 2 one wave per SIMD, 3 packed small-map tiles
 WINO = os.environ.get("E4S_WINO", "1") == "1"        # policy switch of the Winograd F(2,3) kernel (encoders._conv3x3)
 
 
 def wino_eligible(b, h, w, cin, cout, in_stats=False):
     """Shapes e4s_conv_wino_bf16x3_f32 covers, and whether the launch fills the chip (one 16x16-pixel x 128-column tile per block; launches
-    of <= 128 tiles split the input-channel chunks over blocks, csrc/conv_wino.hip:wino_split).  in_stats: the launch folds an
+    of <= 128 tiles split the input-channel chunks over blocks: fills_chip's estimate).  in_stats: the launch folds an
     InstanceNorm into its input transform, whose {mean, rstd} tables live in LDS: Cin <= 1024 (the launcher refuses more)."""
     if not WINO or PRECISION == "f32":
         return False
@@ -514,12 +515,7 @@ def wino_eligible(b, h, w, cin, cout, in_stats=False):
         return False
     if PRECISION == "bf16x3":
         return True
-    tiles = b * (h // 16) * (w // 16) * (cout // 128)
-    if tiles >= BF16X3_MIN_BLOCKS:
-        return True
-    nchunk = cin // 16
-    split = min(nchunk // 2, -(-256 // tiles)) if nchunk >= 4 else 1
-    return tiles * max(split, 1) >= 64
+    return fills_chip(b * (h // 16) * (w // 16) * (cout // 128), cin // 16)
 
 
 def wino_weights(w9):

@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E4S_LIB_PATH") or os.path.join(_HERE, "libe4s_hip.so")      # (E4S_LIB_PATH: A/B runs of two builds)
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -166,6 +166,7 @@ SIGNATURES = {
     "e4s_conv_bf16x3_f32": [ctypes.POINTER(ConvParams), c_p],
     "e4s_conv_bf16x3_ws_floats": [ctypes.POINTER(ConvParams)],
     "e4s_conv_mfma_ws_floats": [ctypes.POINTER(ConvParams), c_i],
+    "e4s_gather_ksplit": [c_l, c_i, c_i],
     "e4s_split_bf16x2_f32": [c_p, c_p, c_l, c_i, c_p],
     "e4s_conv_region_bf16x3_f32": [ctypes.POINTER(ConvParams), c_p, c_p],
     "e4s_conv_region_ws_floats": [ctypes.POINTER(ConvParams)],

@@ -200,6 +200,9 @@ int e4s_upconv_blocks_per_cu(void);    /* diagnostic: occupancy of that kernel a
  * with Cin >= 256 splits its input channels over blocks: e4s_conv_bf16x3_ws_floats(p) > 0, p->splitk_ws required, p->stats_ws not allowed. */
 int e4s_conv_bf16x3_f32(const e4s_conv_params* p, void* stream);
 int64_t e4s_conv_bf16x3_ws_floats(const e4s_conv_params* p);
+/* K splits of a gather-kernel launch of `tiles` 256-pixel x 128-column tiles (ABI v24; host-side policy, no launch): what the launcher
+ * uses unless the output's channel stride is no multiple of 4 (then 1).  The rule is csrc/split_policy.h's gather_split. */
+int e4s_gather_ksplit(int64_t tiles, int cin, int ntaps);
 /* w fp32 [rows][cin] -> out [rows][cin/32][32 hi bf16 | 32 lo bf16] (same byte size), cin % 32 == 0 */
 int e4s_split_bf16x2_f32(const float* w, void* out, int64_t rows, int cin, void* stream);
 
@@ -272,7 +275,7 @@ int e4s_conv_wgrad_f32(const e4s_conv_wgrad_params* p, void* stream);
 int64_t e4s_conv_wgrad_ws_floats(const e4s_conv_wgrad_params* p);
 /* Which kernel e4s_conv_wgrad_f32 launches (host-side policy, no launch; ABI v13): 1 = the split-bf16 kernel (3x3; istride 1 with or without a
  * region map, istride 2 without: both operands as hi + lo bf16, three bf16 MFMAs per product, fp32 accumulate -- the forward kernels'
- * arithmetic, 2^-17-class rounding); 0 = the exact-fp32 MFMA kernel (1x1; everything with env E4S_WGRAD_BF16X3=0). */
+ * arithmetic, 2^-17-class rounding); 0 = the exact-fp32 MFMA kernel (1x1; everything with env E4S_WGRAD_BF16X3=0 in a profiling build). */
 int e4s_conv_wgrad_path(const e4s_conv_wgrad_params* p);
 /* forward-packed weights [ncls][9][Cout][Cin] -> backward layout [ncls][9][Cin][Cout], taps flipped */
 int e4s_pack_taps_bwd_f32(const float* w, float* wt, int ncls, int cout, int cin, void* stream);
