@@ -1214,14 +1214,19 @@ e4s_gather_plan gather_plan(const e4s_conv_params& p) {
     return g;
 }
 
+// same plan, tiles and grid on either kernel: the one-wave-per-SIMD kernel (conv_gather1w.hip) where e4s_gather1w_ok, else the 8-wave kernel
 int launch_gather(const e4s_conv_params& p, hipStream_t st) {
-    auto kern = conv_bf16x3_gather_kernel;
-    static std::atomic<uint64_t> smem_set{0};
-    if (int e = e4s_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM_GATHER, smem_set)) return e;
     const e4s_gather_plan g = gather_plan(p);
     if (g.npix <= 0) return 0;
     if (g.npix * g.ntn >= (1ll << 31)) return (int)hipErrorInvalidValue;
     if (g.ksplit > 1 && (!p.splitk_ws || p.stats_ws)) return (int)hipErrorInvalidValue;
+    if (e4s_gather1w_ok(p)) {
+        if (int e = e4s_launch_gather1w(p, g, st)) return e;
+        return g.ksplit > 1 ? e4s_splitk_epilogue(p, g.ksplit, true, st) : 0;
+    }
+    auto kern = conv_bf16x3_gather_kernel;
+    static std::atomic<uint64_t> smem_set{0};
+    if (int e = e4s_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM_GATHER, smem_set)) return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)(g.ntile * g.ksplit)), dim3(NTHR), SMEM_GATHER, st, p, g.ntn, (int)g.npix, (int)g.ntile, g.ksplit,
                        g.cper);
     E4S_CHECK_LAUNCH();
@@ -1405,6 +1410,13 @@ extern "C" int64_t e4s_conv_bf16x3_ws_floats(const e4s_conv_params* pp) {
     if (p.istride == 2 || p.ntaps == 1) return gather_plan(p).slab_floats;        // raw slabs of the deep few-tile 3x3 launches
     if (p.istride != 1 || p.ntaps != 9 || p.Cin % KC) return 0;
     return p.labels ? e4s_plan_masked(p).slab_floats : plain_plan(p).slab_floats;
+}
+
+// which kernel a gather launch takes (host-side policy, no launch): 0 not a gather launch, 1 the 8-wave kernel, 2 one wave per SIMD
+extern "C" int e4s_conv_gather_path(const e4s_conv_params* pp) {
+    const e4s_conv_params& p = *pp;
+    if (!(p.istride == 2 || p.ntaps == 1)) return 0;
+    return e4s_gather1w_ok(p) ? 2 : 1;
 }
 
 extern "C" int e4s_gather_ksplit(int64_t tiles, int cin, int ntaps) {

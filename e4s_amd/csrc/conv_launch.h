@@ -35,6 +35,8 @@ bool e4s_region_packed(const e4s_conv_params& p);                               
 int e4s_launch_region_select(const e4s_conv_params& p, const int* only_flagged, hipStream_t st);       // conv_bf16x3.hip
 bool e4s_region_rows1w_ok(const e4s_conv_params& p);                                                   // conv_region1w.hip
 int e4s_launch_region_rows1w(const e4s_conv_params& p, const void* w16, int* flags, hipStream_t st, int layout);
+bool e4s_gather1w_ok(const e4s_conv_params& p);                                                        // conv_gather1w.hip
+int e4s_launch_gather1w(const e4s_conv_params& p, const e4s_gather_plan& g, hipStream_t st);           // (K split: the caller runs the second stage)
 int e4s_launch_wino1w(const e4s_conv_params& p, int ntn, int tx_n, int per_img, int ntiles, int grid, hipStream_t st);      // conv_wino1w.hip
 // second stage of every split-K launch (conv_bf16x3.hip): slabs p.splitk_ws[k] are added in order, then noise / bias / activation;
 // slabs_need_out_scale: the slabs are raw sums (the plain kernel's), not yet multiplied by p.out_scale

@@ -76,7 +76,12 @@ def _conv_strided(x, conv, cout, stride, ntaps, want_stats=False, se=None, **kw)
     if strided_bf16x3(b, h, wd, cin, cout, stride, ntaps):
         if getattr(conv, "_e4s_split", None) is None or conv._e4s_split[0] != conv._e4s_pack[0]:
             conv._e4s_split = (conv._e4s_pack[0], K.split_bf16x2(w))
-        return K.conv_mfma(x, w, cout, istride=stride, ntaps=ntaps, w_split=conv._e4s_split[1], want_stats=want_stats, se=se, **kw)
+        frag = None
+        if cout % 128 == 0:               # whole 128-column tiles: the one-wave-per-SIMD gather kernel, weights from the fragment-major image
+            if getattr(conv, "_e4s_frag", None) is None or conv._e4s_frag[0] != conv._e4s_pack[0]:
+                conv._e4s_frag = (conv._e4s_pack[0], K.gather_frag_bf16x2(w))
+            frag = conv._e4s_frag[1]
+        return K.conv_mfma(x, w, cout, istride=stride, ntaps=ntaps, w_split=conv._e4s_split[1], w_frag=frag, want_stats=want_stats, se=se, **kw)
     return K.conv_mfma(x, w, cout, istride=stride, ntaps=ntaps, want_stats=want_stats, se=se, **kw)
 
 

@@ -304,7 +304,7 @@ def f32_plain_split(on=True):
 def conv_mfma(x, w, cout, *, plan=None, istride=1, ostride=1, ntaps=9, ncls=1, in_scale=None, out_scale=None,
               noise=None, noise_w=None, noise_per_channel=False, bias=None, slope=None, act=0, alpha=0.2,
               gain=LRELU_GAIN, spatial=None, anchors=None, labels=None, num_regions=1, w_split=None, in_stats=None,
-              out=None, tap_shift=0, want_stats=False, w_split16=None, se=None):
+              out=None, tap_shift=0, want_stats=False, w_split16=None, se=None, w_frag=None):
     """x NHWC [B,Hi,Wi,Cin]; w [ncls, ntaps, Cout, Cin] -> y NHWC [B,Ho,Wo,Cout].
     anchors = (Ha, Wa); defaults: up-conv (ncls=4) anchors = input grid, output 2x;
     strided conv anchors = output grid.
@@ -312,6 +312,8 @@ def conv_mfma(x, w, cout, *, plan=None, istride=1, ostride=1, ntaps=9, ncls=1, i
     (callers check bf16x3_eligible first -- an ineligible shape is an error, not a silent fp32 run).
     w_split16: (masked layers, with w_split) the 16-channel-chunk split image (split16_bf16x2): the contraction runs on
     e4s_conv_region_bf16x3_f32 (variant-rows kernel; the region-select kernel for tiles / launches it does not take).
+    w_frag: (strided / 1x1 launches, with w_split) the fragment-major split image (gather_frag_bf16x2): where the launch is eligible
+    (Cout % 128 == 0) it runs the one-wave-per-SIMD gather kernel -- the same output bits; without it the 8-wave kernel.
     in_stats: [B,Cin,2] InstanceNorm statistics of x; the normalisation is applied while the input is staged (split-bf16
     kernel only).
     out: write the Cout channels into the FIRST channels of this wider NHWC tensor [B,Ho,Wo,Cy >= Cout] (returned).
@@ -392,6 +394,10 @@ def conv_mfma(x, w, cout, *, plan=None, istride=1, ostride=1, ntaps=9, ncls=1, i
             LAST_REGION_PATH = lib.load().e4s_conv_region_path(ctypes.byref(p))     # 1: 8-wave kernel, 2: one wave per SIMD, 3: packed small-map tiles (tests / bench)
             call("e4s_conv_region_bf16x3_f32", ctypes.byref(p), ptr(w_split16), stream())
             return y
+        if gather_ok:
+            p.w_frag = ptr(w_frag) if w_frag is not None else None
+            global LAST_GATHER_PATH
+            LAST_GATHER_PATH = lib.load().e4s_conv_gather_path(ctypes.byref(p))     # 1: 8-wave kernel, 2: one wave per SIMD (tests / bench)
         nws = lib.load().e4s_conv_bf16x3_ws_floats(ctypes.byref(p))        # split-K partial sums (few-tile launches)
         skws = torch.empty(nws, device=x.device, dtype=torch.float32) if nws else None
         p.splitk_ws = fptr(skws)
@@ -478,6 +484,18 @@ def split_bf16x2(w, out=None):
     return out
 
 
+def gather_frag_bf16x2(w, out=None):
+    """fp32 tap-packed weights [1, ntaps, Cout, Cin] -> the fragment-major split image the one-wave-per-SIMD gather kernel loads its weight
+    fragments from (conv_mfma's w_frag; opaque fp32-typed tensor of the same shape / byte size).  Cin % 32 == 0, Cout % 32 == 0."""
+    w = _f32(w)
+    out = _into(out, tuple(w.shape), w.device)
+    ntaps, cout, cin = w.shape[-3], w.shape[-2], w.shape[-1]
+    if w.numel() != ntaps * cout * cin or lib.load().e4s_gather_frag_bytes(ntaps, cout, cin) != out.numel() * 4:
+        raise RuntimeError("gather_frag_bf16x2: one set of taps [ntaps, Cout, Cin] with Cin % 32 == 0 and Cout % 32 == 0")
+    call("e4s_gather_frag_bf16x2_f32", fptr(w), ptr(out), ntaps, cout, cin, stream())
+    return out
+
+
 def split16_shape(w_shape):
     """Shape of the opaque fp32-typed tensor split16_bf16x2 fills for tap-packed weights of shape w_shape: (k,) + w_shape, k = 2 when Cout % 32 == 0
     (plane-major image + fragment-major image, e4s_split16_bytes), else 1."""
@@ -499,6 +517,7 @@ def split16_bf16x2(w, out=None):
 
 REGION_1W = os.environ.get("E4S_REGION_1W", "1") != "0"        # the library reads the same variable (csrc/conv_region.hip e4s_plan_masked)
 REGION_PACK = os.environ.get("E4S_REGION_PACK", "1") != "0"    # the library reads the same variable (csrc/conv_bf16x3.hip): packed small-map tiles
+LAST_GATHER_PATH = 0           # which kernel the last strided / 1x1 split-bf16 launch took (e4s_conv_gather_path): 1 8-wave kernel, 2 one wave per SIMD
 LAST_REGION_PATH = 0           # which kernel the last masked launch took (e4s_conv_region_path): 1 8-wave rows kernel, 2 one wave per SIMD, 3 packed small-map tiles
 WINO = os.environ.get("E4S_WINO", "1") == "1"        # policy switch of the Winograd F(2,3) kernel (encoders._conv3x3)
 

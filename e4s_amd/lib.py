@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E4S_LIB_PATH") or os.path.join(_HERE, "libe4s_hip.so")      # (E4S_LIB_PATH: A/B runs of two builds)
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -45,7 +45,7 @@ class ConvParams(ctypes.Structure):
         ("noise", c_p), ("noise_w", c_p), ("noise_bstride", c_l), ("noise_per_channel", c_i),
         ("bias", c_p), ("slope", c_p), ("act", c_i), ("alpha", c_f), ("gain", c_f),
         ("in_stats", c_p), ("y_cstride", c_i), ("splitk_ws", c_p), ("stats_ws", c_p), ("stats_slots", c_i), ("tap_shift", c_i),
-        ("split_hint", c_i),
+        ("split_hint", c_i), ("w_frag", c_p),
     ]
 
 
@@ -171,7 +171,10 @@ SIGNATURES = {
     "e4s_conv_region_bf16x3_f32": [ctypes.POINTER(ConvParams), c_p, c_p],
     "e4s_conv_region_ws_floats": [ctypes.POINTER(ConvParams)],
     "e4s_conv_region_path": [ctypes.POINTER(ConvParams)],
+    "e4s_conv_gather_path": [ctypes.POINTER(ConvParams)],
     "e4s_split16_bytes": [ctypes.c_int64, c_i, c_i],
+    "e4s_gather_frag_bytes": [c_i, c_i, c_i],
+    "e4s_gather_frag_bf16x2_f32": [c_p, c_p, c_i, c_i, c_i, c_p],
     "e4s_split16_bf16x2_f32": [c_p, c_p, c_l, c_i, c_i, c_p],
     "e4s_upconv_blocks_per_cu": [],
     "e4s_instnorm_ws_doubles": [c_i, c_i, c_i],
@@ -340,7 +343,7 @@ SIGNATURES = {
     "e4s_scale_rows_f32": [c_p, c_p, c_l, c_i, c_p],
 }
 
-INT64_RETURN = {"e4s_split16_bytes", "e4s_instnorm_ws_doubles", "e4s_conv_bwd_ws_floats", "e4s_grouped_linear_t_ws_floats", "e4s_reduce_parts_ws_floats", "e4s_instnorm_bwd_ws_doubles", "e4s_prelu_bwd_ws_floats", "e4s_conv_wgrad_ws_floats", "e4s_conv_bf16x3_ws_floats", "e4s_conv_region_ws_floats", "e4s_lpips_layer_ws_doubles", "e4s_conv_mfma_ws_floats",
+INT64_RETURN = {"e4s_split16_bytes", "e4s_gather_frag_bytes", "e4s_instnorm_ws_doubles", "e4s_conv_bwd_ws_floats", "e4s_grouped_linear_t_ws_floats", "e4s_reduce_parts_ws_floats", "e4s_instnorm_bwd_ws_doubles", "e4s_prelu_bwd_ws_floats", "e4s_conv_wgrad_ws_floats", "e4s_conv_bf16x3_ws_floats", "e4s_conv_region_ws_floats", "e4s_lpips_layer_ws_doubles", "e4s_conv_mfma_ws_floats",
                 "e4s_cosine_ws_doubles", "e4s_region_mean_ws_floats", "e4s_colsum_ws_floats", "e4s_scale_dot_ws_floats", "e4s_wino_weights_bytes", "e4s_conv_wino_ws_floats", "e4s_rrdb_pack_bytes", "e4s_pconv_pack_bytes", "e4s_rconv_pack_bytes",
                 "e4s_ranger_multi_ws_floats", "e4s_conv3d_pack_bytes", "e4s_conv3dx_pack_bytes"}       # size queries: return a count, not an error code
 

@@ -18,7 +18,7 @@ _GENERATION = 0
 # Every attribute that caches a weight pack on a module (keyed on param_key).  A new cache must be listed here, or a captured
 # train step keeps serving it stale (tests/test_host_logic.py checks the package against this list).
 PACK_ATTRS = (
-    "_e4s_pack", "_e4s_wino", "_e4s_split", "_e4s_wt", "_e4s_wt_fwd",         # encoders / encoder_autograd / stylegan2 ConvLayer
+    "_e4s_pack", "_e4s_wino", "_e4s_split", "_e4s_frag", "_e4s_wt", "_e4s_wt_fwd",         # encoders / encoder_autograd / stylegan2 ConvLayer
     "_e4s_t", "_e4s_stats", "_e4s_head", "_e4s_small", "_e4s_fold",            # criteria (loss networks)
     "_e4s_dpacks",                                                             # disc_autograd
     "_mlp_pack",                                                               # networks.Net3 (stacked LocalMLPs)

@@ -808,7 +808,9 @@ def conv_layer_nhwc(layer, x, x_is_nchw=False):
     gk = dict(istride=2, ntaps=k * k, anchors=anchors, tap_shift=1 if k == 3 else 0, **kw)
     tiles = (b * anchors[0] * anchors[1] + 255) // 256 * (cout // 128 if cout % 128 == 0 else 0)
     if K.PRECISION != "f32" and cout % 128 == 0 and (K.PRECISION == "bf16x3" or tiles >= K.BF16X3_MIN_BLOCKS):
-        return K.conv_mfma(xb, pk["w"], cout, w_split=split(), **gk)
+        if "w_frag" not in pk:
+            pk["w_frag"] = K.gather_frag_bf16x2(pk["w"])
+        return K.conv_mfma(xb, pk["w"], cout, w_split=split(), w_frag=pk["w_frag"], **gk)
     return K.conv_mfma(xb, pk["w"], cout, **gk)
 
 

@@ -161,6 +161,11 @@ typedef struct {
                                 fewer than 256 blocks per sample (the frozen loss networks' 28^2 / 56^2 layers at batch 1-2: one block per CU and
                                 every stage an exposed round trip otherwise).  Same products, another order of fp32 additions; 0 (default): such
                                 maps are never split -- trained networks keep one summation order whatever the policy of the day */
+    const void* w_frag;      /* ABI v25, e4s_conv_bf16x3_f32's strided / 1x1 (gather) launches only: the e4s_gather_frag_bf16x2_f32 image of the same
+                                tap-packed weights, or NULL.  With it, Cout % 128 == 0, an output channel stride that is a multiple of 4 and an input
+                                under 4 GB the launch runs the one-wave-per-SIMD kernel (csrc/conv_gather1w.hip), which loads its weight fragments
+                                straight from this image; same conv output bit for bit.  E4S_GATHER_1W=0 in the environment (read per launch) keeps
+                                every launch on the 8-wave kernel */
 } e4s_conv_params;
 
 /* y = epilogue( sum_{tap,ci} x[anchor*istride + tap - 1, ci] * in_scale[g,ci] * w[cls,tap,co,ci] )
@@ -203,6 +208,13 @@ int64_t e4s_conv_bf16x3_ws_floats(const e4s_conv_params* p);
 /* K splits of a gather-kernel launch of `tiles` 256-pixel x 128-column tiles (ABI v24; host-side policy, no launch): what the launcher
  * uses unless the output's channel stride is no multiple of 4 (then 1).  The rule is csrc/split_policy.h's gather_split. */
 int e4s_gather_ksplit(int64_t tiles, int cin, int ntaps);
+/* ABI v25.  w fp32 tap-packed [ntaps][Cout][Cin] -> the fragment-major split image p->w_frag points at: per (32-channel chunk, tap, 32-column
+ * block, 16-channel k-step) [hi: 64 lanes x 16 B | lo: the same], lane l = column l & 31, channels 8 (l >> 5) .. + 7 -- one wave instruction reads
+ * 1 KB contiguous; the values are e4s_split_bf16x2_f32's.  Cin % 32 == 0, Cout % 32 == 0; `out` holds e4s_gather_frag_bytes(...) bytes (the size of w).
+ * e4s_conv_gather_path(p): which kernel a launch takes (host-side policy, no launch): 0 not a gather launch, 1 the 8-wave kernel, 2 one wave per SIMD. */
+int e4s_gather_frag_bf16x2_f32(const float* w, void* out, int ntaps, int cout, int cin, void* stream);
+int64_t e4s_gather_frag_bytes(int ntaps, int cout, int cin);
+int e4s_conv_gather_path(const e4s_conv_params* p);
 /* w fp32 [rows][cin] -> out [rows][cin/32][32 hi bf16 | 32 lo bf16] (same byte size), cin % 32 == 0 */
 int e4s_split_bf16x2_f32(const float* w, void* out, int64_t rows, int cin, void* stream);
 

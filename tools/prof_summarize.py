@@ -12,7 +12,7 @@ import sys
 from collections import defaultdict
 
 
-CONV_KEYS = ("conv_mfma", "upconv", "conv_bwd", "conv_bf16x3", "conv_c32", "conv_region", "wino")
+CONV_KEYS = ("conv_mfma", "upconv", "conv_bwd", "conv_bf16x3", "conv_c32", "conv_region", "wino", "conv_gather")
 
 
 def short(name):
