@@ -2368,3 +2368,102 @@ def scale_rows(y, m):
         raise RuntimeError("scale_rows: y [..., C] contiguous fp32 and one multiplier per row")
     call("e4s_scale_rows_f32", fptr(y), fptr(_f32(m)), y.numel() // c, c, stream())
     return y
+
+
+# ---- face-vid2vid SPADE decoder (spade.py) -------------------------------------------------
+def _spade_map(t, c, what):
+    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 4 or t.shape[-1] < c:
+        raise RuntimeError(f"{what}: a contiguous fp32 NHWC device buffer of {c} or more channels")
+    return fptr(t), t.shape[-1]
+
+
+def _spade_pack(w_pack, cout, cin, f32, what):
+    f32 = sr_f32() if f32 is None else bool(f32)
+    if getattr(w_pack, "rconv_shape", None) != (cout, cin, 3) or getattr(w_pack, "rconv_f32", None) != f32:
+        raise RuntimeError(f"{what}: w_pack is not rconv_pack's image of a [{cout},{cin},3,3] weight in this precision")
+    return f32
+
+
+def instnorm_stats_into(x, stats, ws, eps=1e-5):
+    """e4s_instnorm_stats_f32 on the contiguous NHWC map x into the caller's stats [B,C,2] and fp64 workspace (instnorm_ws_doubles)."""
+    b, h, w, c = x.shape
+    if x.dtype != torch.float32 or not x.is_contiguous() or tuple(stats.shape) != (b, c, 2) or not stats.is_contiguous() \
+            or ws.dtype != torch.float64 or ws.numel() < lib.load().e4s_instnorm_ws_doubles(b, h * w, c):
+        raise RuntimeError("instnorm_stats_into: x contiguous fp32 NHWC, stats [B,C,2], ws of e4s_instnorm_ws_doubles doubles")
+    call("e4s_instnorm_stats_f32", fptr(x), fptr(stats), None, ptr(ws), b, h * w, c, float(eps), stream())
+    return stats
+
+
+def spade_shared(seg, cin, w_pack, cout, bias, y, *, shift=0, y_coff=0, f32=None):
+    """relu(3x3 conv + bias) of the first cin channels of the NHWC map seg [B,h,w,.], read through the nearest upsampling by 2^shift,
+    -> channels y_coff .. y_coff + cout of y [B,h << shift,w << shift,.].  w_pack: rconv_pack's image of the [cout,cin,3,3] weight."""
+    p = lib.SpadeSharedParams()
+    p.seg, p.seg_cstride = _spade_map(seg, cin, "spade_shared(seg)")
+    p.y, p.y_cstride = _spade_map(y, y_coff + cout, "spade_shared(y)")
+    b, h, w, _ = seg.shape
+    if shift not in (0, 1, 2) or tuple(y.shape[:3]) != (b, h << shift, w << shift):
+        raise RuntimeError(f"spade_shared: shift 0..2 and y of {(b, h << max(shift, 0), w << max(shift, 0))} pixels, got shift {shift}, {tuple(y.shape[:3])}")
+    f32 = _spade_pack(w_pack, cout, cin, f32, "spade_shared")
+    if bias is not None and bias.numel() != cout:
+        raise RuntimeError(f"spade_shared: bias has {bias.numel()} entries for {cout} channels")
+    for name, t in (("w_pack", w_pack), ("y", y), ("bias", bias)):
+        if t is not None and t.device != seg.device:
+            raise RuntimeError(f"spade_shared: {name} is on {t.device}, seg on {seg.device}")
+    p.w, p.bias = fptr(w_pack), fptr(_f32(bias)) if bias is not None else None
+    p.B, p.Hs, p.Ws, p.Cin, p.Cout, p.y_coff, p.shift, p.precision = b, h, w, cin, cout, int(y_coff), int(shift), 1 if f32 else 0
+    call("e4s_spade_shared_f32", ctypes.byref(p), stream())
+    return y
+
+
+def spade_conv(a, a_coff, cin, w_pack, bias, x, stats, y, *, xs=0, act=True, y_coff=0, f32=None):
+    """One SPADE behind its mlp_shared: channels a_coff .. a_coff + cin of the NHWC buffer a [B,H,W,.] -> y[.., y_coff .. y_coff + C)
+    = (x - mean) * rstd * (1 + gamma) + beta, LeakyReLU(0.2) with act; x [B,H >> xs,W >> xs,.] (its first C channels) is read through
+    a nearest x2 upsampling with xs = 1, stats [B,C,2] are instnorm_stats of x.  w_pack: rconv_pack's image of the interleaved
+    [2 C,cin,3,3] weight (row 2 c gamma's, 2 c + 1 beta's), bias [2 C] interleaved the same way."""
+    c = stats.shape[1] if stats.dim() == 3 else -1
+    p = lib.SpadeConvParams()
+    p.a, p.a_cstride = _spade_map(a, a_coff + cin, "spade_conv(a)")
+    p.x, p.x_cstride = _spade_map(x, max(c, 1), "spade_conv(x)")
+    p.y, p.y_cstride = _spade_map(y, y_coff + max(c, 1), "spade_conv(y)")
+    b, h, w, _ = a.shape
+    if xs not in (0, 1) or tuple(x.shape[:3]) != (b, h >> xs, w >> xs) or (x.shape[1] << xs, x.shape[2] << xs) != (h, w):
+        raise RuntimeError(f"spade_conv: x must hold the output's pixels {(b, h, w)} shifted by xs = {xs}, got {tuple(x.shape[:3])}")
+    if tuple(y.shape[:3]) != (b, h, w) or tuple(stats.shape) != (b, c, 2) or stats.dtype != torch.float32 or not stats.is_contiguous():
+        raise RuntimeError(f"spade_conv: y of {(b, h, w)} pixels and contiguous fp32 stats [B,C,2]")
+    f32 = _spade_pack(w_pack, 2 * c, cin, f32, "spade_conv")
+    if bias is None or bias.numel() != 2 * c:
+        raise RuntimeError(f"spade_conv: the interleaved bias has {2 * c} entries")
+    for name, t in (("w_pack", w_pack), ("bias", bias), ("x", x), ("stats", stats), ("y", y)):
+        if t.device != a.device:
+            raise RuntimeError(f"spade_conv: {name} is on {t.device}, a on {a.device}")
+    p.w, p.bias, p.stats = fptr(w_pack), fptr(_f32(bias)), fptr(stats)
+    p.B, p.H, p.W, p.Cin, p.C, p.a_coff, p.xH, p.xW, p.y_coff = b, h, w, cin, c, int(a_coff), x.shape[1], x.shape[2], int(y_coff)
+    p.xs, p.act, p.precision = int(xs), 1 if act else 0, 1 if f32 else 0
+    call("e4s_spade_conv_f32", ctypes.byref(p), stream())
+    return y
+
+
+def spade_tail_pack(w):
+    """conv_img's weight [3,64,3,3] -> [9,3,64] (tap, output, input), e4s_spade_tail_f32's."""
+    if tuple(w.shape) != (3, 64, 3, 3):
+        raise RuntimeError(f"spade_tail_pack: a [3,64,3,3] weight, got {tuple(w.shape)}")
+    return _f32(w).permute(2, 3, 0, 1).reshape(9, 3, 64).contiguous()
+
+
+def spade_tail(x, wp, bias, *, u8=False, nchw=True, logits=None):
+    """sigmoid(conv_img(leaky_relu(x, 0.2))) of the first 64 channels of NHWC x: fp32 (NCHW or NHWC), or with u8 the uint8 NHWC image
+    round_half_even(clamp(v, 0, 1) * 255).  logits: an fp32 [B,3,H,W] buffer that receives the conv's output."""
+    _spade_map(x, 64, "spade_tail(x)")
+    b, h, w, cs = x.shape
+    if tuple(wp.shape) != (9, 3, 64) or bias.numel() != 3 or wp.device != x.device or bias.device != x.device:
+        raise RuntimeError("spade_tail: wp is spade_tail_pack's [9,3,64] and bias [3], on x's device")
+    if logits is not None and (logits.dtype != torch.float32 or tuple(logits.shape) != (b, 3, h, w) or not logits.is_contiguous() or logits.device != x.device):
+        raise RuntimeError(f"spade_tail: logits is a contiguous fp32 buffer {(b, 3, h, w)}")
+    if u8:
+        out = torch.empty(b, h, w, 3, device=x.device, dtype=torch.uint8)
+        yf, yu = None, out
+    else:
+        out = torch.empty((b, 3, h, w) if nchw else (b, h, w, 3), device=x.device, dtype=torch.float32)
+        yf, yu = out, None
+    call("e4s_spade_tail_f32", fptr(x), cs, fptr(_f32(wp)), fptr(_f32(bias)), fptr(yf), 1 if nchw else 0, ptr(yu), fptr(logits), b, h, w, stream())
+    return out

@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E4S_LIB_PATH") or os.path.join(_HERE, "libe4s_hip.so")      # (E4S_LIB_PATH: A/B runs of two builds)
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -145,6 +145,26 @@ class PoseParams(ctypes.Structure):
         ("raw", c_p), ("degrees", c_p), ("rot", c_p), ("value", c_p), ("jacobian", c_p),
         ("B", c_i), ("HW", c_i), ("C", c_i), ("x_cstride", c_i), ("nbins", c_i), ("K", c_i), ("kp_batch", c_i), ("fixed_mask", c_i),
         ("yaw", c_f), ("pitch", c_f), ("roll", c_f),
+    ]
+
+
+class SpadeSharedParams(ctypes.Structure):
+    """Mirror of ``e4s_spade_shared_params`` (include/e4s_hip.h)."""
+    _fields_ = [
+        ("seg", c_p), ("w", c_p), ("bias", c_p), ("y", c_p),
+        ("B", c_i), ("Hs", c_i), ("Ws", c_i), ("Cin", c_i), ("Cout", c_i),
+        ("seg_cstride", c_i), ("y_cstride", c_i), ("y_coff", c_i),
+        ("shift", c_i), ("precision", c_i),
+    ]
+
+
+class SpadeConvParams(ctypes.Structure):
+    """Mirror of ``e4s_spade_conv_params`` (include/e4s_hip.h)."""
+    _fields_ = [
+        ("a", c_p), ("w", c_p), ("bias", c_p), ("x", c_p), ("stats", c_p), ("y", c_p),
+        ("B", c_i), ("H", c_i), ("W", c_i), ("Cin", c_i), ("C", c_i),
+        ("a_cstride", c_i), ("a_coff", c_i), ("x_cstride", c_i), ("xH", c_i), ("xW", c_i), ("y_cstride", c_i), ("y_coff", c_i),
+        ("xs", c_i), ("act", c_i), ("precision", c_i),
     ]
 
 
@@ -341,6 +361,9 @@ SIGNATURES = {
     "e4s_warp3d_f32": [c_p, c_l, c_l, c_l, c_p, c_p] + [c_i] * 5 + [c_p],
     "e4s_occlusion_f32": [c_p, c_i, c_p, c_p, c_p] + [c_i] * 6 + [c_p],
     "e4s_scale_rows_f32": [c_p, c_p, c_l, c_i, c_p],
+    "e4s_spade_shared_f32": [ctypes.POINTER(SpadeSharedParams), c_p],
+    "e4s_spade_conv_f32": [ctypes.POINTER(SpadeConvParams), c_p],
+    "e4s_spade_tail_f32": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p],
 }
 
 INT64_RETURN = {"e4s_split16_bytes", "e4s_gather_frag_bytes", "e4s_instnorm_ws_doubles", "e4s_conv_bwd_ws_floats", "e4s_grouped_linear_t_ws_floats", "e4s_reduce_parts_ws_floats", "e4s_instnorm_bwd_ws_doubles", "e4s_prelu_bwd_ws_floats", "e4s_conv_wgrad_ws_floats", "e4s_conv_bf16x3_ws_floats", "e4s_conv_region_ws_floats", "e4s_lpips_layer_ws_doubles", "e4s_conv_mfma_ws_floats",

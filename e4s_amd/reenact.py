@@ -2,7 +2,7 @@
 keypoints, head pose in degrees, and the transformed keypoints `make_animation` (driven_demo.py:182-211) hands to its generator.
 
 This is everything `make_animation` computes before it calls the generator; the generator's dense motion and 3-D feature warp are
-reenact_warp.py, its SPADE decoder is not provided.  `KPDetector` and `HEEstimator` take the reference's constructor arguments and
+reenact_warp.py, its SPADE decoder spade.py.  `KPDetector` and `HEEstimator` take the reference's constructor arguments and
 hold the reference's parameter tree (modules/keypoint_detector.py, modules/util.py), so a checkpoint's ['kp_detector'] and ['he_estimator'] load with
 load_state_dict(strict=True).  The modules hold parameters only; execution is on channels-last buffers:
 

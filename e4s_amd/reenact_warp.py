@@ -1,8 +1,8 @@
 """face-vid2vid's dense motion and 3-D feature warp (src/pretrained/face_vid2vid/modules/dense_motion.py, generator.py:211-246) --
 MI355X-native.  Everything OcclusionAwareSPADEGenerator.forward does before `self.decoder(out)`: the appearance encoder and its
 reshape into a feature volume, the ResBlock3d stack, the whole DenseMotionNetwork, the 3-D grid_sample warp, `third`, `fourth` and the
-occlusion product.  The result is the map the SPADE decoder reads; the SPADE decoder itself is not provided (it is the one missing
-piece of the re-enactment step).
+occlusion product.  The result is the map the SPADE decoder reads; the SPADE decoder itself is spade.py, whose
+OcclusionAwareSPADEGenerator is FeatureWarp plus that decoder.
 
 `DenseMotionNetwork` and `FeatureWarp` take the reference's constructor arguments and hold the reference's parameter tree
 (`FeatureWarp` without `decoder.*`), so a checkpoint's ['generator'] entry loads with FeatureWarp.load_generator_state_dict.  The

@@ -455,3 +455,48 @@ def synth_vid2vid_keypoints(n, seed=0, jacobian=False):
         sj = eye + 0.2 * torch.randn(1, 15, 3, 3, generator=g, dtype=torch.float32)
         dj = eye + 0.2 * torch.randn(n, 15, 3, 3, generator=g, dtype=torch.float32)
     return {"value": sv, "jacobian": sj}, {"value": dv, "jacobian": dj}
+
+
+def synth_vid2vid_decoder_state_dict(module, seed=0):
+    """Seeded weights of a face-vid2vid SPADEDecoder (the reference's or e4s_amd.spade's: chosen by key and shape only, so both get
+    identical tensors).  Conv weights fan-in scaled, biases 0.1 randn.  The spectral-norm buffers `weight_u` / `weight_v` are what a
+    trained checkpoint holds: unit vectors after two power iterations on the conv's own `weight_orig`, in fp64, from seeded random
+    vectors -- sigma = u . W v is then near the true spectral norm but not equal to it (synth_module_state_dict's BatchNorm-scale rule
+    1 +- 0.1 would be meaningless for them)."""
+    keys = {k: tuple(v.shape) for k, v in module.state_dict().items()}
+    out = {}
+    for k, shape in keys.items():
+        leaf = k.rsplit(".", 1)[-1]
+        if leaf in ("weight_u", "weight_v"):
+            continue
+        x = torch.randn(shape, generator=_gen("vid2vid.dec." + k, seed), dtype=torch.float32)
+        if leaf == "bias":
+            out[k] = 0.1 * x
+        else:
+            fan_in = 1
+            for d in shape[1:]:
+                fan_in *= d
+            out[k] = x / math.sqrt(fan_in)
+    for k, shape in keys.items():
+        stem, leaf = k.rsplit(".", 1)
+        if leaf != "weight_u":
+            continue
+        w = out[stem + ".weight_orig"].double().reshape(shape[0], -1)
+        g = _gen("vid2vid.dec." + k, seed)
+        u = torch.randn(w.shape[0], generator=g, dtype=torch.float64)
+        v = torch.randn(w.shape[1], generator=g, dtype=torch.float64)
+        u, v = u / u.norm(), v / v.norm()
+        for _ in range(2):
+            v = torch.mv(w.t(), u)
+            v = v / v.norm()
+            u = torch.mv(w, v)
+            u = u / u.norm()
+        if keys[stem + ".weight_v"] != (w.shape[1],):
+            raise ValueError(f"synth_vid2vid_decoder_state_dict: {stem}.weight_v has shape {keys[stem + '.weight_v']}")
+        out[k], out[stem + ".weight_v"] = u.float(), v.float()
+    return {k: out[k] for k in keys}
+
+
+def synth_vid2vid_decoder_feature(n, h, w, seed=0):
+    """Seeded float32 [n,256,h,w] input of the SPADE decoder checks: unit normal, every sample different."""
+    return torch.randn(n, 256, h, w, generator=_gen("vid2vid.dec.in", seed), dtype=torch.float32)

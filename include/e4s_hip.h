@@ -1010,6 +1010,49 @@ int e4s_occlusion_f32(const float* x, int x_cstride, const float* w, const float
 /* y [rows,C] *= m [rows], in place; C % 4 == 0 */
 int e4s_scale_rows_f32(float* y, const float* m, int64_t rows, int C, void* stream);
 
+/* ---- face-vid2vid SPADE decoder (ABI v26; e4s_amd/spade.py, csrc/spade.hip; modules/generator.py:121-159, util.py:419-481) ---- */
+/* mlp_shared of the SPADEs of one resolution: y[.., y_coff .. y_coff + Cout) = relu(zero-padded 3x3 conv + bias) on the grid
+ * [B,Hs << shift,Ws << shift], seg [B,Hs,Ws,seg_cstride] (the first Cin channels) being read through the nearest upsampling by
+ * 2^shift (shift 0..2): grid position (gy, gx) reads seg (gy >> shift, gx >> shift), the padding applies on the grid.  w: the
+ * [Cout,Cin,3,3] weight (the SPADEs' weights concatenated along Cout) packed by e4s_rconv_pack_f32 for the same precision; Cin a
+ * multiple of 32, Cout of 64; bias [Cout] or NULL.  y [B,Hs << shift,Ws << shift,y_cstride] must not overlap seg.  precision as in
+ * e4s_rconv_f32; the summation order of an output is (tap, 32-channel chunk, k-step). */
+typedef struct {
+    const float* seg;
+    const float* w;
+    const float* bias;
+    float* y;
+    int B, Hs, Ws, Cin, Cout;
+    int seg_cstride, y_cstride, y_coff;
+    int shift, precision;
+} e4s_spade_shared_params;
+int e4s_spade_shared_f32(const e4s_spade_shared_params* p, void* stream);
+/* One SPADE after its mlp_shared: the 3x3 convs mlp_gamma and mlp_beta over channels a_coff .. a_coff + Cin of a [B,H,W,a_cstride]
+ * as one implicit GEMM to 2 C channels, and the modulation in its epilogue (gamma and beta are never stored):
+ *   y[b,oy,ox,y_coff + c] = (x[b,oy >> xs,ox >> xs,c] - mean[b,c]) * rstd[b,c] * (1 + gamma + bias[2 c]) + (beta + bias[2 c + 1]),
+ *   then v > 0 ? v : 0.2 v when act = 1.
+ * w: the [2 C,Cin,3,3] weight whose row 2 c is mlp_gamma's row c and row 2 c + 1 mlp_beta's row c, packed by e4s_rconv_pack_f32
+ * for the same precision; bias [2 C] interleaved the same way.  x [B,xH,xW,x_cstride] with xH << xs == H and xW << xs == W (xs 0
+ * or 1: x read through a nearest x2 upsampling); stats [B,C,2] = {mean, rstd} of x (e4s_instnorm_stats_f32).  C a multiple of 64,
+ * Cin of 32; channel offsets and strides multiples of 4; y must not overlap a, x or stats. */
+typedef struct {
+    const float* a;
+    const float* w;
+    const float* bias;
+    const float* x;
+    const float* stats;
+    float* y;
+    int B, H, W, Cin, C;
+    int a_cstride, a_coff, x_cstride, xH, xW, y_cstride, y_coff;
+    int xs, act, precision;
+} e4s_spade_conv_params;
+int e4s_spade_conv_f32(const e4s_spade_conv_params* p, void* stream);
+/* sigmoid(conv_img(leaky_relu(x, 0.2))): zero-padded 3x3, 64 -> 3, exact fp32.  x [B,H,W,x_cstride] (the first 64 channels), wp
+ * [9][3][64] (tap, output, input), bias [3].  yf: fp32 [B,3,H,W] (nchw) or [B,H,W,3], or NULL; yu: uint8 [B,H,W,3] =
+ * round_half_even(clamp(v, 0, 1) * 255), or NULL (one of the two is given); logits: the conv's output [B,3,H,W], or NULL. */
+int e4s_spade_tail_f32(const float* x, int x_cstride, const float* wp, const float* bias, float* yf, int nchw, uint8_t* yu, float* logits,
+                       int B, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
