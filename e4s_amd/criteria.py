@@ -1,5 +1,6 @@
-"""Loss networks of the optimisation loop -- MI355X-native.
+"""Loss networks of the optimisation loop and of the train step -- MI355X-native.
 
+`StyleLoss` (src/criteria/style_loss.py:82-221, coach.py:446-450) is described at its class below.
 `IDLoss` (src/criteria/id_loss.py:6-57 over the IR-SE50 `Backbone`, src/models/encoders/model_irse.py:10-69,
 helpers.py:97-119), `LPIPS` (src/criteria/lpips/lpips.py:8-35 over torchvision's AlexNet `features`,
 src/criteria/lpips/networks.py:28-83) and `FaceParsingLoss` (src/criteria/face_parsing/face_parsing_loss.py:20-78 over the
@@ -19,6 +20,10 @@ unchanged; execution is a fixed schedule of HIP kernels on NHWC tensors with a t
 
     parsing UNet encoder            conv + BatchNorm(eval) folded into ONE conv with bias + ReLU epilogue (16-channel maps
                                     zero-padded to the 32-channel K step), e4s_maxpool2_f32, e4s_relu_bwd_f32
+
+    StyleLoss (VGG16 Gram matrices)  e4s_style_prep_f32 (bilinear resize + ImageNet normalisation + mask, NCHW -> NHWC; its adjoint), VGG16
+                                    features[0..22] as conv + bias + ReLU epilogues and e4s_maxpool2_f32, e4s_gram_f32 (exact-fp32 MFMA,
+                                    operands straight from global memory), e4s_gram_mse_f32, e4s_gram_grad_f32 (csrc/gram.hip)
 
 The target image's features are cached per target tensor (the reference recomputes them every step, id_loss.py:33-35).
 """
@@ -761,3 +766,195 @@ class FaceParsingLoss(Module):
         """-> (loss, sim_improvement) as the reference; sim_improvement is a 0-dim tensor."""
         loss, sims = _ParsingLossFn.apply(y_hat, self, self._target_feats(y))
         return loss, (sims - 1.0).mean(1).sum()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# StyleLoss (VGG16 Gram matrices)
+# ---------------------------------------------------------------------------------------------------------------
+VGG16_CFG = (64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512, "M")
+
+
+def vgg16_features():
+    """torchvision.models.vgg16().features (torchvision itself is not a dependency here): indices and shapes as its state_dict has them."""
+    layers, cin = [], 3
+    for v in VGG16_CFG:
+        if v == "M":
+            layers.append(MaxPool2d(kernel_size=2, stride=2))
+        else:
+            layers += [Conv2d(cin, v, kernel_size=3, padding=1), ReLU(inplace=True)]
+            cin = v
+    return Sequential(*layers)
+
+
+class VGG16_Activations(Module):
+    """src/criteria/style_loss.py:82-99: the ModuleList `features` with torchvision's indices (all 31, so that the state_dict keys are the
+    reference's); the native schedule runs up to the deepest tap and never past features[22] -- the reference runs features[23..30] too and
+    throws the result away."""
+
+    LAST = 22
+
+    def __init__(self, feature_idx):
+        super().__init__()
+        self.features = nn.ModuleList(list(vgg16_features())).eval()
+        relu_outs = [i for i, m in enumerate(self.features) if isinstance(m, ReLU) and i <= self.LAST]
+        bad = [i for i in feature_idx if i not in relu_outs]
+        if bad or not feature_idx:
+            raise NotImplementedError(f"VGG16_Activations: taps {bad or list(feature_idx)} -- the native schedule taps ReLU outputs up to "
+                                      f"features[{self.LAST}] only ({relu_outs}); a conv or pool output, or a deeper layer, is not built")
+        self.layer_id_list = sorted(set(int(i) for i in feature_idx))
+        for p in self.parameters():
+            p.requires_grad = False
+
+    def used_convs(self):
+        """indices of the convs the schedule runs: every Conv2d below the deepest tap"""
+        return [i for i, m in enumerate(self.features) if isinstance(m, Conv2d) and i < self.layer_id_list[-1]]
+
+    def features_nhwc(self, x0, tape=None):
+        """x0 NHWC [B,S,S,3] (S % 8 == 0) -> {tap index: NHWC ReLU output}."""
+        L, taps, x = self.features, {}, x0
+        acts, idxs = {}, {}
+        for i in range(self.layer_id_list[-1] + 1):
+            m = L[i]
+            if isinstance(m, Conv2d):
+                if i == 0:
+                    x = K.conv_smallcin(x, _smallcin_pack(m), m.bias.detach(), m.out_channels, 3, 1, 1, relu=True)
+                else:
+                    x = _conv3x3(x, m, m.out_channels, bias=m.bias.detach(), act=1, alpha=0.0, gain=1.0)
+                acts[i + 1] = x                                       # the ReLU at i + 1 is the conv's epilogue
+            elif isinstance(m, MaxPool2d):
+                x, idxs[i] = K.maxpool2(x)
+            if i in self.layer_id_list:
+                taps[i] = x
+        if tape is not None:
+            tape.update(x0=tuple(x0.shape), acts=acts, idxs=idxs)
+        return taps
+
+    def backward_nhwc(self, tape, tap_bwd):
+        """tap_bwd(i, acc): dL/d(tap i) added to acc (None: returned) -> dL/d(x0) NHWC."""
+        L, acts, idxs = self.features, tape["acts"], tape["idxs"]
+        d = None
+        for i in reversed(self.used_convs()):
+            if i + 1 in self.layer_id_list:
+                d = tap_bwd(i + 1, d)
+            du = K.relu_bwd(d, acts[i + 1])
+            if i == 0:
+                return K.conv_smallcin_bwd(du, _smallcin_pack(L[0]), tape["x0"], 3, 1, 1, cache=_smallcin_cache(L[0]))
+            d = _conv3x3(du, _transposed(L[i]), L[i].in_channels)
+            if isinstance(L[i - 1], MaxPool2d):
+                d = K.maxpool2_bwd(d, idxs[i - 1], tuple(acts[i - 2].shape))
+
+    def forward(self, x):
+        """style_loss.py:92-99 on the native schedule: NCHW in, the tapped activations NCHW out (no gradient)."""
+        with torch.no_grad():
+            taps = self.features_nhwc(K.nchw_to_nhwc(x))
+            return [K.nhwc_to_nchw(taps[i]) for i in self.layer_id_list]
+
+
+class _StyleLossFn(torch.autograd.Function):
+    """mean over the taps of mse(Gram(x), Gram(x_hat)) with the gradient back to x (NCHW)."""
+
+    @staticmethod
+    @_plain_split
+    def forward(ctx, x, mod, mask, y_grams):
+        tape = {}
+        taps = mod._taps(x, mask, tape)
+        ids = mod.vgg16_act.layer_id_list
+        loss = torch.empty(1, device=x.device, dtype=torch.float32)
+        terms, diffs = [], []
+        for k, i in enumerate(ids):
+            t, d = K.gram_mse(K.gram(taps[i]), y_grams[k], loss, 1.0 / len(ids), init=k == 0)
+            terms.append(t)
+            diffs.append(d)
+        ctx.mod, ctx.tape, ctx.taps, ctx.diffs, ctx.mask, ctx.in_shape = mod, tape, taps, diffs, mask, tuple(x.shape)
+        terms = torch.cat(terms)
+        ctx.mark_non_differentiable(terms)
+        return loss.reshape(()), terms
+
+    @staticmethod
+    @once_differentiable
+    @_plain_split
+    def backward(ctx, gloss, _gterms):
+        mod = ctx.mod
+        if ctx.tape is None:
+            raise RuntimeError("StyleLoss: the activation tape was released by the first backward; run the forward again "
+                               "(retain_graph / double backward through this node are not supported)")
+        g = gloss.reshape(1).to(torch.float32).contiguous()
+        ids = mod.vgg16_act.layer_id_list
+
+        def tap_bwd(i, acc):
+            f = ctx.taps[i]
+            n, h, w, c = f.shape
+            coef = 4.0 / (float(n * c) ** 2 * len(ids) * n * h * w * c)
+            return K.gram_grad(f, ctx.diffs[ids.index(i)], g, coef, addend=acc)
+        dx0 = mod.vgg16_act.backward_nhwc(ctx.tape, tap_bwd)
+        dx = K.style_prep_bwd(dx0, ctx.mask, ctx.in_shape, mod.normalize)
+        ctx.tape = ctx.taps = ctx.diffs = None
+        return dx, None, None, None
+
+
+class StyleLoss(Module):
+    """src/criteria/style_loss.py:102-221 (the reference's signature plus `weights`).  `weights`: a path to, or the dict of, a
+    torchvision vgg16 state dict (the reference downloads the pretrained one; `features.N.*` are taken, `classifier.*` and everything past
+    features[22] are ignored, a missing used key is an error); also $E4S_VGG16_WEIGHTS.  `in_size` is the side the images are resized to
+    (the reference hard-codes 256 and ignores its own option)."""
+
+    def __init__(self, VGG16_ACTIVATIONS_LIST=[21], normalize=False, distance="l2", in_size=256, weights=None):
+        super().__init__()
+        if distance != "l2":
+            raise NotImplementedError(f"StyleLoss(distance={distance!r}): only the 'l2' distance coach.py:155-158 uses is built")
+        if in_size % 8 or in_size <= 0:
+            raise NotImplementedError(f"StyleLoss(in_size={in_size}): three MaxPool2d(2) need a multiple of 8")
+        self.vgg16_act = VGG16_Activations(list(VGG16_ACTIVATIONS_LIST))
+        self.vgg16_act.eval()
+        self.in_size, self.normalize, self.distance = in_size, bool(normalize), distance
+        if not isinstance(weights, dict):
+            weights = weights or os.environ.get("E4S_VGG16_WEIGHTS")
+            weights = torch.load(weights, map_location="cpu") if _have_weights(
+                "StyleLoss (weights= / $E4S_VGG16_WEIGHTS: torchvision's vgg16 state dict)", weights) else None
+        if weights is not None:
+            self.load_vgg16(weights)
+        self._target = None
+
+    def load_vgg16(self, sd):
+        """Take `features.N.{weight,bias}` (also under `vgg16_act.`) of a torchvision vgg16 state dict."""
+        sd = {(k[len("vgg16_act."):] if k.startswith("vgg16_act.") else k): v for k, v in sd.items()}
+        used = self.vgg16_act.used_convs()
+        missing = [f"features.{i}.{leaf}" for i in used for leaf in ("weight", "bias") if f"features.{i}.{leaf}" not in sd]
+        if missing:
+            raise KeyError(f"StyleLoss: the VGG16 state dict lacks {missing}")
+        with torch.no_grad():
+            for i, m in enumerate(self.vgg16_act.features):
+                if isinstance(m, Conv2d) and i <= VGG16_Activations.LAST and f"features.{i}.weight" in sd:
+                    m.weight.copy_(sd[f"features.{i}.weight"])
+                    m.bias.copy_(sd[f"features.{i}.bias"])
+
+    def _taps(self, x, mask, tape=None):
+        x0 = K.style_prep(x.detach(), mask, (self.in_size, self.in_size), self.normalize)
+        return self.vgg16_act.features_nhwc(x0, tape)
+
+    @staticmethod
+    def _mask(mask):
+        return None if mask is None else mask.detach().to(torch.float32).contiguous()
+
+    @_plain_split
+    def grams(self, x, mask=None):
+        """The Gram matrices [NC,NC] of the taps of x (no gradient), in the order of the sorted tap list."""
+        with torch.no_grad():
+            taps = self._taps(x, self._mask(mask))
+            return [K.gram(taps[i]) for i in self.vgg16_act.layer_id_list]
+
+    def _target_grams(self, x_hat, mask):
+        key = _target_key(x_hat) + ((_target_key(mask) + (tuple(mask.stride()),)) if mask is not None else (None,))
+        if self._target is None or self._target[0] != key or self._target[1] is not x_hat:
+            self._target = (key, x_hat, mask, self.grams(x_hat, mask))         # holds x_hat AND the mask (see _target_key)
+        return self._target[3]
+
+    def forward(self, x, x_hat, mask_x=None, mask_x_hat=None):
+        """style_loss.py:133-202; the gradient goes to x only (coach.py:447 passes the reconstruction as x, the image as x_hat)."""
+        if x_hat.requires_grad:
+            raise NotImplementedError("StyleLoss: x_hat is the target (coach.py:447: the input image) -- a gradient to it is not built")
+        if (mask_x is None) != (mask_x_hat is None):
+            raise ValueError("StyleLoss: mask_x and mask_x_hat come together (style_loss.py:163-164)")
+        loss, terms = _StyleLossFn.apply(x, self, self._mask(mask_x), self._target_grams(x_hat, mask_x_hat))
+        self.last_terms = terms                                          # per-tap mse, before the mean over the taps (a device tensor)
+        return loss

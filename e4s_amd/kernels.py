@@ -1546,6 +1546,68 @@ def cosine_bwd(a, b, coef, gout, gmul, da_acc=None):
     return da
 
 
+# ---- VGG16 Gram-matrix StyleLoss (csrc/gram.hip) ----------------------------------------------------------------
+def style_prep(x, mask, out_hw, normalize):
+    """NCHW image [B,3,H,W] (+ mask [B,1,Hm,Wm] or None) -> NHWC [B,oh,ow,3]: bilinear resize, ImageNet normalisation, times the
+    bilinearly resized mask (style_loss.py:143-170)."""
+    x = _f32(x)
+    b, c, h, w = x.shape
+    if c != 3:
+        raise ValueError(f"style_prep: a 3-channel image, got {c} channels")
+    hm, wm = _style_mask(mask, b)
+    oh, ow = out_hw
+    y = torch.empty(b, oh, ow, 3, device=x.device, dtype=torch.float32)
+    call("e4s_style_prep_f32", fptr(x), fptr(mask), fptr(y), b, h, w, hm, wm, oh, ow, 1 if normalize else 0, stream())
+    return y
+
+
+def _style_mask(mask, b):
+    if mask is None:
+        return 0, 0
+    if mask.dim() != 4 or mask.shape[0] != b or mask.shape[1] != 1 or mask.dtype != torch.float32 or not mask.is_contiguous():
+        raise ValueError(f"style_prep: the mask is a contiguous fp32 [B,1,Hm,Wm] tensor, got {tuple(mask.shape)} {mask.dtype}")
+    return mask.shape[2], mask.shape[3]
+
+
+def style_prep_bwd(dy, mask, in_shape, normalize):
+    """The transpose of style_prep's linear map: dy NHWC [B,oh,ow,3] -> dx NCHW in_shape."""
+    b, c, h, w = in_shape
+    hm, wm = _style_mask(mask, b)
+    oh, ow = dy.shape[1:3]
+    dx = torch.empty(in_shape, device=dy.device, dtype=torch.float32)
+    call("e4s_style_prep_bwd_f32", fptr(_f32(dy)), fptr(mask), fptr(dx), b, h, w, hm, wm, oh, ow, 1 if normalize else 0, stream())
+    return dx
+
+
+def gram(f):
+    """NHWC tap [N,H,W,C] -> G [NC,NC] = F F^T / (N H W C) over the [N C, H W] view of the batch (style_loss.py:213-221)."""
+    n, h, w, c = f.shape
+    nws = lib.load().e4s_gram_ws_floats(n, h * w, c)
+    if nws <= 0:
+        raise ValueError(f"gram: C % 64 == 0 and N C <= 16384, got N {n}, C {c}")
+    g = torch.empty(n * c, n * c, device=f.device, dtype=torch.float32)
+    ws = torch.empty(nws, device=f.device, dtype=torch.float32)
+    call("e4s_gram_f32", fptr(f), fptr(g), fptr(ws), n, h * w, c, stream())
+    return g
+
+
+def gram_mse(gx, gy, acc, weight, init=False):
+    """-> (term [1] = mean((gx - gy)^2), D = gx - gy); acc[0] (+)= weight * term (init: acc[0] = weight * term)."""
+    d = torch.empty_like(gx)
+    term = torch.empty(1, device=gx.device, dtype=torch.float32)
+    ws = torch.empty(lib.load().e4s_gram_mse_ws_doubles(gx.numel()), device=gx.device, dtype=torch.float64)
+    call("e4s_gram_mse_f32", fptr(gx), fptr(gy), fptr(d), fptr(term), fptr(acc), float(weight), 1 if init else 0, ptr(ws), gx.numel(), stream())
+    return term, d
+
+
+def gram_grad(f, d, gloss, coef, addend=None):
+    """dF[n,p,c] = addend + coef * gloss[0] * sum_j A[p][j] D[j][n C + c] (A the Gram's operand, D symmetric)."""
+    n, h, w, c = f.shape
+    df = torch.empty_like(f)
+    call("e4s_gram_grad_f32", fptr(f), fptr(d), fptr(gloss), float(coef), fptr(addend), fptr(df), n, h * w, c, stream())
+    return df
+
+
 # ---- BiSeNet face parser (face_parser.py) ---------------------------------------------------
 def parser_preprocess(src, taps):
     """uint8 NHWC [B,H,W,3] or fp32 NCHW [B,3,H,W] in [0,1] -> the parser's input NHWC [B,H/2,W/2,3]: bicubic /2 (reflect),

@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E4S_LIB_PATH") or os.path.join(_HERE, "libe4s_hip.so")      # (E4S_LIB_PATH: A/B runs of two builds)
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -312,6 +312,13 @@ SIGNATURES = {
     "e4s_cosine_f32": [c_p, c_p, c_p, c_p, c_i, c_l, c_p],
     "e4s_cosine_ws_doubles": [c_i, c_l],
     "e4s_cosine_bwd_f32": [c_p, c_p, c_p, c_p, c_f, c_p, c_i, c_l, c_i, c_p],
+    "e4s_style_prep_f32": [c_p, c_p, c_p] + [c_i] * 8 + [c_p],
+    "e4s_style_prep_bwd_f32": [c_p, c_p, c_p] + [c_i] * 8 + [c_p],
+    "e4s_gram_f32": [c_p, c_p, c_p, c_i, c_i, c_i, c_p],
+    "e4s_gram_ws_floats": [c_i, c_i, c_i],
+    "e4s_gram_mse_f32": [c_p, c_p, c_p, c_p, c_p, c_f, c_i, c_p, c_l, c_p],
+    "e4s_gram_mse_ws_doubles": [c_l],
+    "e4s_gram_grad_f32": [c_p, c_p, c_p, c_f, c_p, c_p, c_i, c_i, c_i, c_p],
     "e4s_parser_preprocess_f32": [c_p, c_i, c_p, c_i, c_i, c_i, ctypes.POINTER(c_f), c_p],
     "e4s_maxpool3s2p1_f32": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
     "e4s_add_relu_f32": [c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_p],
@@ -368,7 +375,7 @@ SIGNATURES = {
 
 INT64_RETURN = {"e4s_split16_bytes", "e4s_gather_frag_bytes", "e4s_instnorm_ws_doubles", "e4s_conv_bwd_ws_floats", "e4s_grouped_linear_t_ws_floats", "e4s_reduce_parts_ws_floats", "e4s_instnorm_bwd_ws_doubles", "e4s_prelu_bwd_ws_floats", "e4s_conv_wgrad_ws_floats", "e4s_conv_bf16x3_ws_floats", "e4s_conv_region_ws_floats", "e4s_lpips_layer_ws_doubles", "e4s_conv_mfma_ws_floats",
                 "e4s_cosine_ws_doubles", "e4s_region_mean_ws_floats", "e4s_colsum_ws_floats", "e4s_scale_dot_ws_floats", "e4s_wino_weights_bytes", "e4s_conv_wino_ws_floats", "e4s_rrdb_pack_bytes", "e4s_pconv_pack_bytes", "e4s_rconv_pack_bytes",
-                "e4s_ranger_multi_ws_floats", "e4s_conv3d_pack_bytes", "e4s_conv3dx_pack_bytes"}       # size queries: return a count, not an error code
+                "e4s_ranger_multi_ws_floats", "e4s_conv3d_pack_bytes", "e4s_conv3dx_pack_bytes", "e4s_gram_ws_floats", "e4s_gram_mse_ws_doubles"}       # size queries: return a count, not an error code
 
 _lib = None
 

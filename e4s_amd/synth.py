@@ -318,6 +318,23 @@ def synth_module_state_dict(module, seed=0, tag="crit."):
     return out
 
 
+VGG16_FEATURE_CONVS = ((0, 3, 64), (2, 64, 64), (5, 64, 128), (7, 128, 128), (10, 128, 256), (12, 256, 256), (14, 256, 256),
+                       (17, 256, 512), (19, 512, 512), (21, 512, 512))          # (index in torchvision's vgg16().features, Cin, Cout) up to 22
+
+
+def synth_vgg16_state_dict(seed=0, prefix="features."):
+    """Seeded weights in the layout of torchvision's vgg16 state dict, `features.0` .. `features.21` (StyleLoss taps nothing deeper; the
+    real weights are a download).  Chosen by key and shape only.  He-scaled weights (x sqrt(2 / fan_in)) keep the second moment of the
+    activations through the ten ReLU convs -- they neither die nor blow up -- and the biases are 0.1 randn, not zero."""
+    out = {}
+    for idx, cin, cout in VGG16_FEATURE_CONVS:
+        kw, kb = f"features.{idx}.weight", f"features.{idx}.bias"
+        w = torch.randn((cout, cin, 3, 3), generator=_gen("vgg16." + kw, seed), dtype=torch.float32)
+        out[prefix + f"{idx}.weight"] = w * math.sqrt(2.0 / (9 * cin))
+        out[prefix + f"{idx}.bias"] = 0.1 * torch.randn((cout,), generator=_gen("vgg16." + kb, seed), dtype=torch.float32)
+    return out
+
+
 def synth_rrdb_state_dict(net, seed=0):
     """Seeded weights of an RRDBNet (the reference's or e4s_amd.sr's: chosen by key and shape only): synth_module_state_dict with
     the dense blocks' conv weights x 0.1 -- the reference's own init scale (rrdbnet_arch.py:29) -- and conv_last scaled so that most

@@ -118,11 +118,14 @@ def w_norm_loss(latent, latent_avg=None, start_from_latent_avg=True):
 
 
 class LossOpts:
-    """The loss weights of train_options.py:44-57 (defaults as shipped; style_lambda -- the VGG16 gram-matrix loss of
-    coach.py:446-450, 0 as shipped, needs torchvision's VGG16 -- is not built)."""
+    """The loss weights of train_options.py:44-57 (defaults as shipped).  style_lambda: the VGG16 Gram-matrix loss of coach.py:446-450
+    on the skin-masked images (criteria.StyleLoss as crit['style']), 0 as shipped (train_options.py:55); style_loss_norm: 1 = ImageNet
+    normalisation in front of VGG16 (train_options.py:59; the StyleLoss is constructed with normalize=style_loss_norm == 1)."""
 
     def __init__(self, face_parsing_lambda=0.1, id_lambda=0.1, l2_lambda=1.0, lpips_lambda=0.8, g_adv_lambda=0.01,
-                 r1_lambda=10.0, d_every=15, d_reg_every=-1, lpips_sizes=(1024, 512, 256), w_norm_lambda=0.0):
+                 r1_lambda=10.0, d_every=15, d_reg_every=-1, lpips_sizes=(1024, 512, 256), w_norm_lambda=0.0, style_lambda=0.0,
+                 style_loss_norm=1):
+        self.style_lambda, self.style_loss_norm = style_lambda, style_loss_norm
         self.face_parsing_lambda, self.id_lambda, self.l2_lambda = face_parsing_lambda, id_lambda, l2_lambda
         self.lpips_lambda, self.g_adv_lambda, self.r1_lambda = lpips_lambda, g_adv_lambda, r1_lambda
         self.d_every, self.d_reg_every, self.lpips_sizes = d_every, d_reg_every, tuple(lpips_sizes)
@@ -130,7 +133,7 @@ class LossOpts:
 
 
 class TrainIteration:
-    """net: Net3 in train mode; disc: Discriminator or None (train_D False); crit: dict with optional 'lpips', 'id', 'parsing'
+    """net: Net3 in train mode; disc: Discriminator or None (train_D False); crit: dict with optional 'lpips', 'id', 'parsing', 'style'
     (e4s_amd.criteria modules); opt / opt_d: optimisers over net's / disc's trainable parameters; averager / averager_d:
     ddp.GradAverager (N > 1) or None; net_ema: EMA copy of net or None; ema_decay: coach.py:29's ACCUM by default."""
 
@@ -160,7 +163,7 @@ class TrainIteration:
         self.global_step = 0
 
     # ---- coach.py:403-453 -------------------------------------------------------------------------------------------
-    def calc_loss(self, img, recon, latent=None):
+    def calc_loss(self, img, recon, latent=None, mask=None):
         lo, terms, fns, keys = self.lo, {}, [], []
 
         def term(key, weight, fn):
@@ -183,12 +186,19 @@ class TrainIteration:
                 raise RuntimeError("w_norm_lambda > 0 needs the latent (Net3.forward(..., return_latents=True))")
             term("w_norm", lo.w_norm_lambda,
                  lambda: w_norm_loss(latent, self.core.latent_avg, getattr(self.core.opts, "start_from_latent_avg", True)))
+        if lo.style_lambda > 0 and "style" in self.crit:
+            # coach.py:446-450: the last term, recon and img under the skin mask (mask == 3); on the step's own stream (never a side term below)
+            if mask is None:
+                raise RuntimeError("style_lambda > 0 needs the skin mask (calc_loss(..., mask=onehot[:, 3:4]))")
+            term("style", lo.style_lambda, lambda: self.crit["style"](recon, img, mask_x=mask, mask_x_hat=mask))
         if self.fork_losses and recon.is_cuda and len(fns) > 1:
             from .optim import forked_sum
             # fork_losses == "id": ONE side branch, the identity network (the longest chain), the rest on the current stream under it
             side = [keys.index("id")] if (self.fork_losses == "id" and "id" in keys and not os.environ.get("E4S_FORK_SIDE")) else None
             if self.fork_losses == "id" and "id" not in keys:
                 side = []                                         # no identity term: one chain
+            if "style" in keys and side is None:
+                side = [i for i, k in enumerate(keys) if k != "style"]     # "all": every term but the style term, which stays on the step's stream
             loss = forked_sum(0.0, fns, inputs=(recon, img), side_terms=side)      # ((0 + parsing) + id) + l2 + lpips: coach.py:403-453's order
         else:
             loss = 0.0
@@ -206,7 +216,7 @@ class TrainIteration:
                 recon, _, latent = self.net(img, onehot, return_latents=True, **fwd)
             else:
                 recon, _ = self.net(img, onehot, **fwd)
-            loss, terms = self.calc_loss(img, recon, latent)
+            loss, terms = self.calc_loss(img, recon, latent, mask=onehot[:, 3:4] if self.lo.style_lambda > 0 else None)
             if self.disc is not None:
                 terms["g_adv"] = adv_g_loss(self.disc(recon))
                 loss = loss + self.lo.g_adv_lambda * terms["g_adv"]

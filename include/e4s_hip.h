@@ -697,6 +697,32 @@ int64_t e4s_cosine_ws_doubles(int B, int64_t D);
 int e4s_cosine_bwd_f32(const float* a, const float* b, const float* coef, const float* gout, float gmul, float* da, int B,
                        int64_t D, int accumulate, void* stream);
 
+/* ---- VGG16 Gram-matrix StyleLoss (ABI v27; src/criteria/style_loss.py:82-221, coach.py:446-450; csrc/gram.hip) ---------------- */
+/* style_loss.py:143-170 in one pass: y NHWC [B,oh,ow,3] = mask_r * norm(bilinear(x)) with x NCHW [B,3,H,W], F.interpolate(mode="bilinear",
+ * align_corners=False, no antialias) to oh x ow, norm(v) = ((v + 1) / 2 - mean) / std with the ImageNet constants (normalize = 0: v), and
+ * mask_r the mask [B,1,Hm,Wm] resized the same way (mask NULL: none).  Any sizes.  *_bwd: dx NCHW [B,3,H,W] = the transpose of that linear
+ * map applied to dy [B,oh,ow,3] -- a gather over the output pixels that read an image pixel, in (oy, ox) order: deterministic, every
+ * element of dx is written. */
+int e4s_style_prep_f32(const float* x, const float* mask, float* y, int B, int H, int W, int Hm, int Wm, int oh, int ow, int normalize,
+                       void* stream);
+int e4s_style_prep_bwd_f32(const float* dy, const float* mask, float* dx, int B, int H, int W, int Hm, int Wm, int oh, int ow,
+                           int normalize, void* stream);
+/* gram_matrix (style_loss.py:213-221) of an NHWC tap F [N,HW,C]: G [NC,NC] = A^T A / (N HW C) with A[p][n C + c] = F[n,p,c], the cross-sample
+ * blocks included.  Exact-fp32 MFMA; the pixels are split into slices whose partial tiles (ws: e4s_gram_ws_floats(N, HW, C) floats) are
+ * added in slice order in fp64, and G[i][j], G[j][i] are written from the same sum: G == G^T and two calls agree bit for bit.  C % 64 != 0 (or
+ * N C > 16384): hipErrorInvalidValue before any launch, and a workspace size of 0. */
+int e4s_gram_f32(const float* F, float* G, float* ws, int N, int HW, int C, void* stream);
+int64_t e4s_gram_ws_floats(int N, int HW, int C);
+/* one layer of the loss (custom_loss, style_loss.py:26-33, "l2"): D[i] = gx[i] - gy[i], term[0] = mean_i D[i]^2 (ordered; fp64 above the
+ * per-thread sums; ws: e4s_gram_mse_ws_doubles(n) doubles), acc[0] = (init ? 0 : acc[0]) + weight * term[0]. */
+int e4s_gram_mse_f32(const float* gx, const float* gy, float* D, float* term, float* acc, float weight, int init, double* ws, int64_t n,
+                     void* stream);
+int64_t e4s_gram_mse_ws_doubles(int64_t n);
+/* gradient of that layer w.r.t. the tap: dF[n,p,c] = (addend ? addend[n,p,c] : 0) + coef * gloss[0] * sum_j A[p][j] D[j][n C + c] (D symmetric;
+ * coef = 4 / ((NC)^2 L N HW C) for the mean over L layers; gloss is read on the device).  F 16-byte aligned, C % 64 == 0. */
+int e4s_gram_grad_f32(const float* F, const float* D, const float* gloss, float coef, const float* addend, float* dF, int N, int HW, int C,
+                      void* stream);
+
 /* ---- BiSeNet face parser (ABI v15; e4s_amd/face_parser.py, src/pretrained/face_parsing/) ------------------------------ */
 /* BicubicDownSample(factor 2) + clamp(0, 1) + ImageNet (x - mean) / std in one pass (face_parsing_demo.py:15-73,152-156):
  * src uint8 NHWC [B,H,W,3] (is_u8 = 1; decoded pixels, read as x / 255) or fp32 NCHW [B,3,H,W] in [0,1]; dst fp32 NHWC
