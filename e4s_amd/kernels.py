@@ -2529,3 +2529,65 @@ def spade_tail(x, wp, bias, *, u8=False, nchw=True, logits=None):
         yf, yu = out, None
     call("e4s_spade_tail_f32", fptr(x), cs, fptr(_f32(wp)), fptr(_f32(bias)), fptr(yf), 1 if nchw else 0, ptr(yu), fptr(logits), b, h, w, stream())
     return out
+
+
+# ---- the joins of the face-swap pipeline (pipeline.py; csrc/pipeline.hip) ----------------------
+def _join_arg(t, what, dtype, dims, last=None):
+    """Wrong dtype / shape / layout: ValueError; a tensor off the device: RuntimeError."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != dims or (last is not None and t.shape[-1] != last):
+        got = f"{tuple(t.shape)} {t.dtype}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{what}, got {got}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{what.split(':')[0]} runs on the ROCm device only (no CPU path)")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}, contiguous")
+    return t
+
+
+def _join_out(out, shape, dtype, like, what):
+    if out is None:
+        return torch.empty(shape, device=like.device, dtype=dtype)
+    if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != dtype or not out.is_contiguous():
+        raise ValueError(f"{what} is a contiguous {dtype} buffer {tuple(shape)}")
+    if out.device != like.device:
+        raise RuntimeError(f"{what} is on {out.device}, the input on {like.device}")
+    return out
+
+
+def resize_aa4(images_u8, out=None):
+    """skimage.transform.resize(im / 255.0, (H/4, W/4)) of scikit-image 0.20 for uint8 NHWC images [B,H,W,3] -> fp32 [B,H/4,W/4,3]
+    in [0,1]; H and W multiples of 4, at least 8 (a single reflection at the border must suffice)."""
+    x = _join_arg(images_u8, "resize_aa4: uint8 NHWC images [B,H,W,3]", torch.uint8, 4, 3)
+    b, h, w, _ = x.shape
+    if b < 1 or h % 4 or w % 4 or h < 8 or w < 8:
+        raise ValueError(f"resize_aa4: H and W must be multiples of 4 and at least 8, got {h} x {w} (batch {b})")
+    out = _join_out(out, (b, h // 4, w // 4, 3), torch.float32, x, "resize_aa4: out")
+    call("e4s_resize_aa4_u8_f32", ptr(x), fptr(out), b, h, w, stream())
+    return out
+
+
+def driven_seam(pred, enlarge=True, out=None, out_enlarged=None):
+    """The decoder's fp32 NCHW prediction [N,3,h,w] in [0,1] -> (uint8 BGR [N,h,w,3] = (pred * 255).astype(uint8), truncated; that
+    frame enlarged x4 by cv2.resize's 8-bit INTER_LINEAR arithmetic, uint8 BGR [N,4h,4w,3], or None with enlarge=False)."""
+    x = _join_arg(pred, "driven_seam: an fp32 NCHW prediction [N,3,h,w]", torch.float32, 4)
+    n, c, h, w = x.shape
+    if c != 3 or n < 1 or h < 1 or w < 1:
+        raise ValueError(f"driven_seam: an fp32 NCHW prediction [N,3,h,w], got {tuple(x.shape)}")
+    out = _join_out(out, (n, h, w, 3), torch.uint8, x, "driven_seam: out")
+    big = _join_out(out_enlarged, (n, 4 * h, 4 * w, 3), torch.uint8, x, "driven_seam: out_enlarged") if enlarge else None
+    call("e4s_driven_seam_f32", fptr(x), ptr(out), ptr(big), n, h, w, stream())
+    return out, big
+
+
+def face_to_net(faces_u8, bgr=False, rgb=True, net=True, out_rgb=None, out_net=None):
+    """uint8 NHWC faces [B,H,W,3] (BGR with bgr) -> (uint8 RGB NHWC, what the parser reads; fp32 NCHW [B,3,H,W] = (v / 255 - 0.5) /
+    0.5, the encoder's input, bit for bit torchvision's ToTensor + Normalize(0.5, 0.5)).  rgb / net = False: that output is None.
+    out_net may be a slice of a larger buffer (GraphedFaceSwap.static)."""
+    x = _join_arg(faces_u8, "face_to_net: uint8 NHWC faces [B,H,W,3]", torch.uint8, 4, 3)
+    b, h, w, _ = x.shape
+    if b < 1 or h < 1 or w < 1 or not (rgb or net or out_rgb is not None or out_net is not None):
+        raise ValueError(f"face_to_net: a non-empty batch and one output or both, got {tuple(x.shape)}")
+    o_rgb = _join_out(out_rgb, (b, h, w, 3), torch.uint8, x, "face_to_net: out_rgb") if rgb or out_rgb is not None else None
+    o_net = _join_out(out_net, (b, 3, h, w), torch.float32, x, "face_to_net: out_net") if net or out_net is not None else None
+    call("e4s_face_to_net_u8", ptr(x), 1 if bgr else 0, ptr(o_rgb), fptr(o_net), b, h, w, stream())
+    return o_rgb, o_net

@@ -1,0 +1,214 @@
+"""The face swap as one thing on the device: scripts/face_swap.py:150-331 `faceSwapping_pipeline`, frames in, swapped frames out.
+
+Every stage already had a native form; this module chains them and adds the four joins between them that did not
+(csrc/pipeline.hip), so that a frame goes up once, comes down once and in between leaves the device only as the detector's list of
+boxes (FaceRestorer.process, one device-to-host copy per frame):
+
+    reference (face_swap.py)                                       here
+    -------------------------------------------------------------  -----------------------------------------------------------
+     1  :179-192  crop_and_align_face                               align.crop_faces_by_quads
+     2  :194      skimage resize(im / 255.0, (256, 256))            K.resize_aa4                  (e4s_resize_aa4_u8_f32)
+     3  :195      faceParsing_demo(T)                               parser.parse(T)
+     4  :203      drive_source_demo(S_256, [T_256], ..)             reenactor.run(S_256, T_256)   (one source encode, B drivings)
+     5  :204      (pred * 255).astype(np.uint8), [:, :, ::-1];      K.driven_seam                 (e4s_driven_seam_f32)
+                  face_enhancement.py:66 cv2.resize to the SR size
+     6  face_enhancement.py:64  srmodel.process(img)                sr.upscale(pred_bgr, bgr=True)
+     7  face_enhancement.py:68-108                                  restorer.process(enlarged, background=sr_frame), per frame
+     8  :209-228  D, ToTensor + Normalize, faceParsing_demo(D)      K.face_to_net(D, bgr=True)    (e4s_face_to_net_u8), parser.parse
+     9  :230-231  ToTensor + Normalize of T                         K.face_to_net(T)
+    10  :253      swap_head_mask_revisit_considerGlass              postproc.swap_head_mask_revisit_considerGlass
+    11  :228-273  labelMap2OneHot x 3, style swap, generator        postproc.labelMap2OneHot(out=...), GraphedFaceSwap / face_swap_core
+    12  :276-311  masks, smooth_face_boundry / blending             postproc.stitch
+    13  :313-327  PERSPECTIVE transform + alpha_composite           align.swap_into_frames
+
+Landmarks stay the caller's business (align.compute_quad(lm68) makes the quad crop_faces_by_quads takes): dlib and face_alignment
+are not part of the reference tree.  PIL's resize of un-cropped frames, SegNeXt parsing and FaceRestorer(in_size != out_size) are
+outside."""
+import numpy as np
+import torch
+
+from . import align, postproc
+from . import kernels as K
+from .networks import GraphedFaceSwap, face_swap_core
+
+FACE = 1024                 # the aligned crop (crop_and_align_face's output size)
+LABELS = 512                # the parser's label maps
+TAPS = ("S_256", "T_256", "pred_bgr", "enlarged", "sr", "D_bgr", "D_labels", "T_labels", "swapped_labels", "hole", "swapped_face",
+        "stitched")
+
+
+def _frames(t, what, dims):
+    """A uint8 device tensor of `dims` dimensions whose last is 3: wrong dtype / shape ValueError, CPU tensor RuntimeError."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != dims or t.shape[-1] != 3 or t.numel() == 0:
+        got = f"{tuple(t.shape)} {t.dtype}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"FaceSwapPipeline.swap: {what} is a uint8 RGB tensor {'[B,H,W,3]' if dims == 4 else '[H,W,3]'}, got {got}")
+    if not t.is_cuda:
+        raise RuntimeError(f"FaceSwapPipeline.swap: {what} must be on the ROCm device (no CPU path)")
+    return t.contiguous()
+
+
+def _quads(q, n, what):
+    try:
+        q = align._quads(q)
+    except RuntimeError as e:
+        raise ValueError(f"FaceSwapPipeline.swap: {what}: {e}") from None
+    if len(q) != n:
+        raise ValueError(f"FaceSwapPipeline.swap: {len(q)} {what} for {n} frames")
+    return q
+
+
+class FaceSwapPipeline(object):
+    """faceSwapping_pipeline with every stage on the device.
+
+    net        an e4s_amd.networks.Net3, or any callable swap(driven, driven_mask, target, target_mask, swapped_mask, noise=...)
+               -> fp32 [B,3,1024,1024] in [-1,1] (face_swap_core's signature behind its net; needs graph=False)
+    reenactor  .run(source [256,256,3] fp32, driving [B,256,256,3] fp32) -> fp32 [B,256,256,3] in [0,1]   (spade.Reenactor)
+    sr         .upscale(uint8 BGR [B,256,256,3], bgr=True) -> uint8 BGR [B,1024,1024,3]                   (sr.RealESRNet)
+    restorer   .process(frame uint8 BGR [1024,1024,3], background=...) -> (restored frame, ..)            (face_paste.FaceRestorer
+               with a detector)
+    parser     .parse(uint8 RGB [B,1024,1024,3]) -> uint8 labels [B,512,512] of the 12 E4S classes        (face_parser.FaceParser)
+    batch      the swap's batch: with graph=True a GraphedFaceSwap(net, batch) is captured on first use and replayed per chunk of
+               `batch` targets, the join kernels writing its static inputs in place; a final partial chunk runs eagerly
+    noise      the generator's noise maps as face_swap_core takes them; default: drawn once, here, with a fixed seed."""
+
+    def __init__(self, net, reenactor, sr, restorer, parser, *, batch=1, lap_bld=False, outer_dilation=5, graph=True, noise=None):
+        self.is_net = hasattr(net, "get_style_vectors")
+        if not self.is_net and not callable(net):
+            raise TypeError("FaceSwapPipeline: net is a Net3 or a callable with face_swap_core's arguments (without the net)")
+        for obj, meth, what in ((reenactor, "run", "reenactor"), (sr, "upscale", "sr"), (restorer, "process", "restorer"),
+                                (parser, "parse", "parser")):
+            if not callable(getattr(obj, meth, None)):
+                raise TypeError(f"FaceSwapPipeline: {what} needs a .{meth}() method")
+        if int(batch) < 1:
+            raise ValueError("FaceSwapPipeline: batch >= 1")
+        if graph and not self.is_net:
+            raise ValueError("FaceSwapPipeline: graph=True captures a Net3; a callable swap runs with graph=False")
+        self.net, self.reenactor, self.sr, self.restorer, self.parser = net, reenactor, sr, restorer, parser
+        self.batch, self.lap_bld, self.outer_dilation, self.graph = int(batch), bool(lap_bld), int(outer_dilation), bool(graph)
+        self.num_cls = int(net.opts.num_seg_cls) if self.is_net else int(getattr(net, "num_seg_cls", 12))
+        if noise is None and self.is_net:
+            dev = next(net.parameters()).device
+            gen = torch.Generator(device="cpu").manual_seed(0)
+            noise = [torch.randn(n.shape, generator=gen).to(dev) for n in net.G.make_noise()]
+        self.noise = noise
+        self.graphed = None
+
+    # ---- step 11 for one chunk -------------------------------------------------------------------------------------------
+    def _graphed(self):
+        if self.graphed is None:
+            g = GraphedFaceSwap(self.net, self.batch, img_size=FACE, mask_size=LABELS, noise_batch=self.noise[0].shape[0])
+            for dst, src in zip(g.noise, self.noise):
+                dst.copy_(src)
+            self.graphed = g
+        return self.graphed
+
+    def _swap_chunk(self, d_bgr, t_rgb, t_lab, taps):
+        """Steps 8-12 for n <= batch frames: restored BGR faces D, target faces T, target labels -> the stitched uint8 faces."""
+        n = d_bgr.shape[0]
+        replay = self.graph and n == self.batch
+        if replay:
+            g = self._graphed()
+            driven, d_oh, target, t_oh, s_oh = g.static
+        else:
+            driven = d_oh = target = t_oh = s_oh = None
+        d_rgb, driven = K.face_to_net(d_bgr, bgr=True, out_net=driven)                                  # 8
+        d_lab = self.parser.parse(d_rgb)
+        _, target = K.face_to_net(t_rgb, rgb=False, out_net=target)                                     # 9
+        for lab, what in ((d_lab, "parser.parse(D)"), (t_lab, "the target labels")):
+            if lab.dtype != torch.uint8 or tuple(lab.shape) != (n, LABELS, LABELS):
+                raise RuntimeError(f"FaceSwapPipeline: {what} must be uint8 [{n},{LABELS},{LABELS}], got {tuple(lab.shape)} {lab.dtype}")
+        d_lab, t_lab = d_lab.contiguous(), t_lab.contiguous()
+        s_lab, hole = postproc.swap_head_mask_revisit_considerGlass(d_lab, t_lab)                       # 10
+        d_oh = postproc.labelMap2OneHot(d_lab[:, None], self.num_cls, out=d_oh)                         # 11
+        t_oh = postproc.labelMap2OneHot(t_lab[:, None], self.num_cls, out=t_oh)
+        s_oh = postproc.labelMap2OneHot(s_lab[:, None], self.num_cls, out=s_oh)
+        if replay:
+            face = g.replay()
+        elif self.is_net:
+            face = face_swap_core(self.net, driven, d_oh, target, t_oh, s_oh, noise=self.noise)
+        else:
+            face = self.net(driven, d_oh, target, t_oh, s_oh, noise=self.noise)
+        stitched = postproc.stitch(face, t_rgb, s_lab, hole, self.lap_bld, self.outer_dilation)         # 12
+        if taps is not None:
+            for k, v in (("D_labels", d_lab), ("swapped_labels", s_lab), ("hole", hole), ("swapped_face", face.clone() if replay else face),
+                         ("stitched", stitched)):
+                taps.setdefault(k, []).append(v)
+        return stitched
+
+    # ---- the pipeline ----------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def swap(self, source_u8, targets_u8, *, source_quad=None, target_quads=None, target_labels=None, taps=None):
+        """source_u8 uint8 RGB [Hs,Ws,3], targets_u8 uint8 RGB [B,H,W,3], both on the device -> uint8 RGB [B,H,W,3].
+        source_quad [4,2] and target_quads [B,4,2] (align.compute_quad): faces are cropped to 1024^2 and the swap goes back into the
+        target frames (need_crop); target_quads only: the source is a 1024^2 face already (only_target_crop); neither: source and
+        targets are 1024^2 faces and the stitched faces are returned.  target_labels: uint8 [B,512,512], replaces the target parse
+        (the reference's target_mask).  taps: a dict that receives every intermediate (TAPS)."""
+        src, tgt = _frames(source_u8, "source_u8", 3), _frames(targets_u8, "targets_u8", 4)
+        b = tgt.shape[0]
+        if taps is not None and not isinstance(taps, dict):
+            raise ValueError("FaceSwapPipeline.swap: taps is a dict (or None)")
+        if source_quad is not None and target_quads is None:
+            raise ValueError("FaceSwapPipeline.swap: a source quad needs target quads (need_crop); target quads alone are only_target_crop")
+        sq = _quads(source_quad, 1, "source quads") if source_quad is not None else None
+        tq = _quads(target_quads, b, "target quads") if target_quads is not None else None
+        if sq is None and tuple(src.shape) != (FACE, FACE, 3):
+            raise ValueError(f"FaceSwapPipeline.swap: without a source quad the source is a {FACE} x {FACE} face (PIL's resize of an "
+                             f"un-cropped frame is not provided), got {tuple(src.shape)}")
+        if tq is None and tuple(tgt.shape[1:]) != (FACE, FACE, 3):
+            raise ValueError(f"FaceSwapPipeline.swap: without target quads the targets are {FACE} x {FACE} faces (PIL's resize of "
+                             f"un-cropped frames is not provided), got {tuple(tgt.shape)}")
+        if target_labels is not None:
+            if not isinstance(target_labels, torch.Tensor) or target_labels.dtype != torch.uint8 or tuple(target_labels.shape) != (b, LABELS, LABELS):
+                raise ValueError(f"FaceSwapPipeline.swap: target_labels is uint8 [{b},{LABELS},{LABELS}]")
+            if not target_labels.is_cuda:
+                raise RuntimeError("FaceSwapPipeline.swap: target_labels must be on the ROCm device (no CPU path)")
+        if src.device != tgt.device:
+            raise RuntimeError("FaceSwapPipeline.swap: source and targets are on different devices")
+
+        s_face = align.crop_faces_by_quads(src[None], sq, FACE) if sq is not None else src[None]              # 1
+        t_face = align.crop_faces_by_quads(tgt, tq, FACE) if tq is not None else tgt
+        s_256, t_256 = K.resize_aa4(s_face), K.resize_aa4(t_face)                                             # 2
+        t_lab = self.parser.parse(t_face) if target_labels is None else target_labels.contiguous()            # 3
+        pred = self.reenactor.run(s_256[0], t_256)                                                            # 4
+        if not isinstance(pred, torch.Tensor) or pred.dtype != torch.float32 or tuple(pred.shape) != (b, FACE // 4, FACE // 4, 3):
+            raise RuntimeError(f"FaceSwapPipeline: reenactor.run must return fp32 [{b},{FACE // 4},{FACE // 4},3] frames")
+        pred_bgr, enlarged = K.driven_seam(pred.permute(0, 3, 1, 2).contiguous())                             # 5 (Reenactor: a view)
+        sr_frames = self.sr.upscale(pred_bgr, bgr=True)                                                       # 6
+        if tuple(sr_frames.shape) != tuple(enlarged.shape) or sr_frames.dtype != torch.uint8:
+            raise RuntimeError(f"FaceSwapPipeline: sr.upscale must return uint8 {tuple(enlarged.shape)} frames")
+        d_bgr = torch.stack([self.restorer.process(enlarged[i], background=sr_frames[i])[0] for i in range(b)])   # 7
+        if taps is not None:
+            taps.update(S_256=s_256, T_256=t_256, pred_bgr=pred_bgr, enlarged=enlarged, sr=sr_frames, D_bgr=d_bgr, T_labels=t_lab)
+        parts = [self._swap_chunk(d_bgr[i:i + self.batch], t_face[i:i + self.batch], t_lab[i:i + self.batch], taps)
+                 for i in range(0, b, self.batch)]                                                            # 8-12
+        stitched = parts[0] if len(parts) == 1 else torch.cat(parts)
+        if taps is not None:
+            for k in ("D_labels", "swapped_labels", "hole", "swapped_face", "stitched"):
+                taps[k] = taps[k][0] if len(taps[k]) == 1 else torch.cat(taps[k])
+        return align.swap_into_frames(stitched, tgt, tq) if tq is not None else stitched                      # 13
+
+    def validate(self):
+        """GraphedFaceSwap.validate() of the captured swap, if there is one (one host sync)."""
+        if self.graphed is not None:
+            self.graphed.validate()
+
+
+def faceSwapping_pipeline(source, target, pipeline, target_mask=None, need_quads=None):
+    """scripts/face_swap.py:150 for images on the host: source, target numpy / PIL RGB images -> the swapped target as a numpy
+    uint8 [H,W,3] array.  One upload, one download.  need_quads: None (both are 1024^2 faces), (source_quad, target_quad) as
+    align.compute_quad(lm68) returns them (need_crop) or (None, target_quad) (only_target_crop).  target_mask: a 12-class uint8
+    [512,512] label map that replaces the parse of the target."""
+    dev = next(pipeline.net.parameters()).device if pipeline.is_net else torch.device("cuda")
+
+    def up(img, what):
+        a = np.asarray(img)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] < 3:
+            raise ValueError(f"faceSwapping_pipeline: {what} is an RGB PIL image or an HWC uint8 array")
+        return torch.from_numpy(np.ascontiguousarray(a[:, :, :3])).to(dev)
+    sq, tq = (None, None) if need_quads is None else need_quads
+    labels = None
+    if target_mask is not None:
+        labels = torch.from_numpy(np.ascontiguousarray(np.asarray(target_mask, dtype=np.uint8)))[None].to(dev)
+    out = pipeline.swap(up(source, "source"), up(target, "target")[None], source_quad=sq, target_quads=None if tq is None else [tq],
+                        target_labels=labels)
+    return out[0].cpu().numpy()

@@ -13,11 +13,15 @@ def _u8(t):
     return t.contiguous()
 
 
-def labelMap2OneHot(label, num_cls):
-    """src/utils/torch_utils.py:166-172: label [B,1,H,W] (uint8 or int64 ids < num_cls) -> one-hot fp32 [B,num_cls,H,W]."""
+def labelMap2OneHot(label, num_cls, out=None):
+    """src/utils/torch_utils.py:166-172: label [B,1,H,W] (uint8 or int64 ids < num_cls) -> one-hot fp32 [B,num_cls,H,W].
+    `out`: write into this contiguous fp32 [B,num_cls,H,W] buffer (e.g. a GraphedFaceSwap.static mask)."""
     b, _, h, w = label.shape
     lab = label.to(torch.uint8).contiguous() if label.dtype != torch.uint8 else _u8(label)
-    out = torch.empty(b, num_cls, h, w, device=label.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(b, num_cls, h, w, device=label.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (b, num_cls, h, w) or not out.is_contiguous() or out.device != label.device:
+        raise RuntimeError(f"labelMap2OneHot: out must be a contiguous fp32 [{b},{num_cls},{h},{w}] tensor on the labels' device")
     call("e4s_onehot_u8_f32", ptr(lab), fptr(out), b, num_cls, h, w, stream())
     return out
 

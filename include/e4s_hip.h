@@ -1079,6 +1079,22 @@ int e4s_spade_conv_f32(const e4s_spade_conv_params* p, void* stream);
 int e4s_spade_tail_f32(const float* x, int x_cstride, const float* wp, const float* bias, float* yf, int nchw, uint8_t* yu, float* logits,
                        int B, int H, int W, void* stream);
 
+/* ---- the joins of the face-swap pipeline (ABI v28; e4s_amd/pipeline.py, csrc/pipeline.hip; scripts/face_swap.py:194-225) ---- */
+/* skimage.transform.resize(x / 255.0, (H/4, W/4)) of scikit-image 0.20 (anti-aliased, order 1, mode 'reflect'): src uint8
+ * [B,H,W,3] -> dst fp32 [B,H/4,W/4,3] in [0,1].  Per axis dst(i) = sum_k t[k] src(mirror(4 i - 5 + k)), k = 0..13, t[k] = (g[k] +
+ * g[k-1]) / 2 with g the normalised Gaussian of sigma 1.5 and radius 6 (zero outside its 13 taps) and mirror the reflection about
+ * the edge pixels (-1 -> 1, n -> n - 2).  H and W: multiples of 4, at least 8.  A sample's values do not depend on B. */
+int e4s_resize_aa4_u8_f32(const uint8_t* src, float* dst, int B, int H, int W, void* stream);
+/* The driven frames between the decoder and GPEN.  pred fp32 [N,3,h,w] (RGB planes, values in [0,1]) -> out_u8 uint8 BGR
+ * [N,h,w,3] = (uint8)(pred * 255) with the fp32 product truncated (numpy's astype), and, unless NULL, enlarged_u8 uint8 BGR
+ * [N,4h,4w,3] = cv2.resize(out_u8, (4w, 4h)) by OpenCV's 8-bit INTER_LINEAR arithmetic: per axis f = (d + 0.5) / 4 - 0.5, s =
+ * floor(f), f -= s; s < 0: s = 0, f = 0; s >= n - 1: s = n - 1, f = 0; c1 = round(2048 f), c0 = 2048 - c1; along x S = src[s] a0 +
+ * src[min(s + 1, n - 1)] a1 (int32), then along y dst = (((b0 (S0 >> 4)) >> 16) + ((b1 (S1 >> 4)) >> 16) + 2) >> 2. */
+int e4s_driven_seam_f32(const float* pred, uint8_t* out_u8, uint8_t* enlarged_u8, int N, int h, int w, void* stream);
+/* src uint8 [B,H,W,3], RGB or (bgr = 1) BGR -> rgb_u8 uint8 RGB [B,H,W,3] and net_f32 fp32 [B,3,H,W] = (v / 255 - 0.5) / 0.5 of the
+ * RGB planes, in fp32 in this order (torchvision's ToTensor + Normalize(0.5, 0.5)).  Either output may be NULL, not both. */
+int e4s_face_to_net_u8(const uint8_t* src, int bgr, uint8_t* rgb_u8, float* net_f32, int B, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
