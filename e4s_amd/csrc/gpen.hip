@@ -111,6 +111,7 @@ __global__ void minibatch_stddev_kernel(const float* __restrict__ x, float* __re
 extern "C" int e4s_conv1x1_small_f32(const float* x, const float* w, const float* bias, float* y, int B, int HW, int Cin,
                                      int Cout, int y_cstride, float scale, int act, float alpha, float gain, void* stream) {
     if (Cin < 1 || Cin > 4 || Cout % 4) return (int)hipErrorInvalidValue;
+    if (y_cstride && (y_cstride % 4 || y_cstride < Cout)) return (int)hipErrorInvalidValue;      // 16-byte stores at y + bp * y_cstride + co
     const int64_t n = (int64_t)B * HW * (Cout / 4);
     if (n <= 0) return 0;
     hipLaunchKernelGGL(conv1x1_small_kernel, grid1(n), dim3(256), 0, as_stream(stream), x, w, bias, y, (int64_t)HW, Cin,

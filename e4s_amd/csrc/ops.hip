@@ -256,9 +256,12 @@ extern "C" int e4s_upfirdn2d_f32(const float* x, const float* k, float* y, int m
                                  int pad_y0, int pad_y1, void* stream) {
     if (up_x < 1 || up_y < 1 || down_x < 1 || down_y < 1 || kh < 1 || kw < 1 || kh > 16 || kw > 16)
         return (int)hipErrorInvalidValue;
-    const int out_h = (in_h * up_y + pad_y0 + pad_y1 - kh) / down_y + 1;     // upfirdn2d_kernel.cu:167-168
-    const int out_w = (in_w * up_x + pad_x0 + pad_x1 - kw) / down_x + 1;
-    if (out_h <= 0 || out_w <= 0 || major <= 0 || minor <= 0) return 0;
+    // a negative numerator is an empty output: C's truncating division would round it up to one row or column that the caller,
+    // who sizes y with a flooring division (kernels.upfirdn2d_raw), never allocated
+    const int num_h = in_h * up_y + pad_y0 + pad_y1 - kh, num_w = in_w * up_x + pad_x0 + pad_x1 - kw;
+    if (num_h < 0 || num_w < 0 || major <= 0 || minor <= 0) return 0;
+    const int out_h = num_h / down_y + 1;     // upfirdn2d_kernel.cu:167-168
+    const int out_w = num_w / down_x + 1;
     if (up_x == 1 && up_y == 1 && down_x == 1 && down_y == 1 && minor % 4 == 0 && minor >= 8 && minor <= 1024 && kh * kw <= 64 &&
         major <= 65535) {
         const int ppb = 256 / (minor / 4);

@@ -71,6 +71,8 @@ def upfirdn2d_raw(x, kernel, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0,
     kh, kw = kernel.shape
     out_h = (in_h * up_y + pad_y0 + pad_y1 - kh) // down_y + 1
     out_w = (in_w * up_x + pad_x0 + pad_x1 - kw) // down_x + 1
+    if out_h <= 0 or out_w <= 0:          # the kernel does not fit the padded input: nothing to compute, nothing to launch
+        return torch.empty(major, max(out_h, 0), max(out_w, 0), minor, device=x.device, dtype=torch.float32)
     y = torch.empty(major, out_h, out_w, minor, device=x.device, dtype=torch.float32)
     call("e4s_upfirdn2d_f32", fptr(x), fptr(kernel), fptr(y), major, in_h, in_w, minor, kh, kw, up_x, up_y,
          down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, stream())

@@ -44,7 +44,8 @@ int e4s_fused_bias_act_f32(const float* x, const float* b, const float* ref, flo
 
 /* Up-FIR-down on x viewed as [major, in_h, in_w, minor]      upfirdn2d_kernel.cu:52-137,140-272
  * (true convolution: kernel flipped; negative pads crop).  y is [major, out_h, out_w, minor] with
- * out = (in*up + pad0 + pad1 - k) / down + 1.  Any up/down >= 1 and kernel size <= 16x16
+ * out = floor((in*up + pad0 + pad1 - k) / down) + 1; in*up + pad0 + pad1 - k < 0 on either axis is an empty output
+ * (returns 0, nothing is launched, y is not touched).  Any up/down >= 1 and kernel size <= 16x16
  * (the reference leaves unmatched modes undefined, .cu:172-175,216). */
 int e4s_upfirdn2d_f32(const float* x, const float* k, float* y, int major, int in_h, int in_w, int minor,
                       int kh, int kw, int up_x, int up_y, int down_x, int down_y,
@@ -384,7 +385,8 @@ int e4s_region_mean_bwd_f32(const float* dcodes, const uint8_t* labels, int Hm, 
 
 /* ---- GPEN FullGenerator / Discriminator support ---------------------------------- */
 /* 1x1 conv with tiny Cin (<= 4; the 3 -> C stem ConvLayer, gpen_model.py:658, model.py:756): x NCHW [B,Cin,HW],
- * w [Cout,Cin], y NHWC (channel stride y_cstride or Cout): act(x.w*scale + bias), act 1 = leaky-relu(alpha)*gain */
+ * w [Cout,Cin], y NHWC (channel stride y_cstride or Cout): act(x.w*scale + bias), act 1 = leaky-relu(alpha)*gain.
+ * Cout % 4 == 0; a y_cstride that is no multiple of 4 or is below Cout is refused (16-byte stores). */
 int e4s_conv1x1_small_f32(const float* x, const float* w, const float* bias, float* y, int B, int HW, int Cin, int Cout,
                           int y_cstride, float scale, int act, float alpha, float gain, void* stream);
 /* y[pix, coff + c] = lrelu(noise_w[0]*feat[pix, c] + bias[c], alpha)*gain: the noise half of GPEN's concatenating
