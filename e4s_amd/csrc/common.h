@@ -18,6 +18,15 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// a * b rounded on its own: the product carries no `contract` flag, so no later add can fuse with it under hipcc's default
+// -ffp-contract=fast-honor-pragmas (__fmul_rn is a plain operator in this ROCm's headers and does fuse; stitch.hip has the story).
+// The per-channel noise term noise_w * noise[pix][co] of the conv epilogues: the per-pixel term is such a product too, rounded by
+// its trip through the tile's row table.
+__device__ __forceinline__ float e4s_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
 // wave64 all-lanes sum
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

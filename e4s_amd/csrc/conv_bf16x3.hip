@@ -113,7 +113,11 @@ struct TileId {          // one 16x16-pixel x BN-column output tile (x one K spl
 // VAR: profiling variants (builds with -DE4S_ABLATIONS select them with env E4S_BF16X3_ABL; results are WRONG for VAR >= 3;
 // product builds only instantiate VAR = 0): 1 s_setprio(1) around the MFMA groups, 2 no scheduling pins, 3 MFMAs + barriers
 // only (no fragment reads, no staging), 4 MFMAs only, 5 everything but the MFMAs
-template <typename C, int XF, bool SHUF, int VAR = 0>
+// PC: per-channel noise, NHWC [Bn][Ho][Wo][Cout] (the editor's maps): instead of the row table's term the epilogue loads 16 bytes per
+//   lane at the output store's own address pattern, multiplies by noise_w (rounded on its own, as the table's term is) and takes the
+//   values back to the accumulators' layout with the quad transpose, which is its own inverse.  With SHUF the phase of column n
+//   moves the PIXEL ((ph >> 1) rows, (ph & 1) columns), the channel is n % Cout.  A separate instantiation: PC = false is the kernel as it was
+template <typename C, int XF, bool SHUF, int VAR = 0, bool PC = false>
 __global__ __launch_bounds__(PNTHR) void conv_bf16x3_kernel(const e4s_conv_params p, const int ntn, const int tx_n,
                                                             const int per_img, const int ntiles, const int ksplit,
                                                             const int cper) {
@@ -163,7 +167,7 @@ __global__ __launch_bounds__(PNTHR) void conv_bf16x3_kernel(const e4s_conv_param
 #pragma unroll
             for (int ph = 0; ph < NZ; ++ph) {
                 float nz = 0.f;
-                if (valid && p.noise)
+                if (!PC && valid && p.noise)
                     nz = p.noise_w[0] * p.noise[(int64_t)id.tb * p.noise_bstride + (int64_t)(oy + (ph >> 1)) * p.Wo + ox + (ph & 1)];
                 s_nz[(buf * BM + tid) * NZ + ph] = nz;
             }
@@ -297,7 +301,10 @@ __global__ __launch_bounds__(PNTHR) void conv_bf16x3_kernel(const e4s_conv_param
         for (int chunk = cur.c_lo; chunk < cur.c_hi; ++chunk) {
             const bool last_chunk = (chunk + 1 == cur.c_hi);
             // owner of chunk cg+1 (whose halo is fetched during this chunk) and of the stage after this chunk's last
-            const TileId& own = last_chunk ? nxt : cur;
+            // (PC: a copy -- selecting between the two by reference left this instantiation's tile ids in scratch memory)
+            TileId own_pc;
+            if (PC) own_pc = last_chunk ? nxt : cur;
+            const TileId& own = PC ? own_pc : (last_chunk ? nxt : cur);
             const bool have_nc = !last_chunk || has_next;
             const int c_n = last_chunk ? nxt.c_lo : chunk + 1;
             const float* xb_n = p.x + (size_t)own.tb * img_stride + c_n * KC;
@@ -422,7 +429,11 @@ __global__ __launch_bounds__(PNTHR) void conv_bf16x3_kernel(const e4s_conv_param
             const float* sn = s_nz + mbuf * BM * NZ;
             float osc[TN], bsv[TN], slp[TN];
             int coff[TN], nzi[TN];
+            int ncoff[PC ? TN : 1];                    // PC: coff for the noise map's channel stride (Cout)
             const int ycs = p.y_cstride ? p.y_cstride : p.Cout;
+            const float nw = PC ? p.noise_w[0] : 0.f;
+            // PC: the noise map of the tile's sample, shifted so that the OUTPUT pixel offset (s_out) indexes it
+            const float* nzb = PC ? p.noise + ((int64_t)cur.tb * p.noise_bstride - (int64_t)cur.tb * p.Ho * p.Wo) * p.Cout : nullptr;
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn) {
                 const int n = cur.n0 + (wn * TN + tn) * 32 + li;
@@ -432,6 +443,7 @@ __global__ __launch_bounds__(PNTHR) void conv_bf16x3_kernel(const e4s_conv_param
                 bsv[tn] = p.bias ? p.bias[co] : 0.f;
                 slp[tn] = (p.act == 2) ? p.slope[co] : p.alpha;
                 coff[tn] = ((ph >> 1) * p.Wo + (ph & 1)) * ycs + co;
+                if (PC) ncoff[tn] = ((ph >> 1) * p.Wo + (ph & 1)) * p.Cout + co;
                 nzi[tn] = ph;
             }
             const float gain = (p.act == 1) ? p.gain : 1.f;
@@ -451,6 +463,18 @@ __global__ __launch_bounds__(PNTHR) void conv_bf16x3_kernel(const e4s_conv_param
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     float v[TN][4];
+                    float nzv[PC ? TN : 1][4];
+                    if (PC && !raw) {
+                        const int offn = so[(wm * TM + tm) * 32 + (li & 3) + 8 * g + 4 * kh];
+#pragma unroll
+                        for (int tn = 0; tn < TN; ++tn) {
+                            f32x4 n4 = {0.f, 0.f, 0.f, 0.f};
+                            if (offn >= 0) n4 = *reinterpret_cast<const f32x4*>(nzb + (int64_t)offn * p.Cout + ncoff[tn] - (li & 3));
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) nzv[tn][e] = e4s_mul_rn(nw, n4[e]);
+                            quad_transpose4(nzv[tn][0], nzv[tn][1], nzv[tn][2], nzv[tn][3], li);
+                        }
+                    }
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int r = 4 * g + i;
@@ -460,7 +484,7 @@ __global__ __launch_bounds__(PNTHR) void conv_bf16x3_kernel(const e4s_conv_param
                         for (int tn = 0; tn < TN; ++tn) {
                             float t = acc[tm][tn][r];
                             if (!raw) {
-                                t = t * osc[tn] + sn[row * NZ + (SHUF ? nzi[tn] : 0)] + bsv[tn];
+                                t = t * osc[tn] + (PC ? nzv[tn][i] : sn[row * NZ + (SHUF ? nzi[tn] : 0)]) + bsv[tn];
                                 if (do_act) t = (t > 0.f ? t : t * slp[tn]) * gain;
                             }
                             v[tn][i] = t;
@@ -584,7 +608,8 @@ static_assert(XPIECE * 9 >= XITEMS && XPIECE <= NTHR, "extended halo split");
 // row's style fragment comes from global memory once per chunk (the [B][R][Cin] table stays in L2; the LDS slice could not hold 9 x 16 rows),
 // d[image][region] is read per row by the epilogue.  tx_n = images per tile, tiles_per_cls = tiles per class; the K split goes down to one
 // chunk per block (pack_split).  Weight staging, MFMA loop, scheduling pins, stores and the ordered second stage are the unpacked kernel's.
-template <int WN_, int SPL, bool SCAN = false, bool PACK = false>
+// PC: per-channel noise [Bn][Ho][Wo][Cout], read beside the store as in the plain kernel (a separate instantiation)
+template <int WN_, int SPL, bool SCAN = false, bool PACK = false, bool PC = false>
 __global__ __launch_bounds__(NTHR) void conv_bf16x3_region_kernel(const e4s_conv_params p, const int ntn,
                                                                   const int tx_n, const int per_img,
                                                                   const int tiles_per_cls, const int ksplit,
@@ -644,7 +669,7 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_region_kernel(const e4s_conv
         float nz = 0.f;
         int r = 0;
         if (valid) {
-            if (p.noise) nz = p.noise_w[0] * p.noise[(int64_t)img * p.noise_bstride + (int64_t)oy * p.Wo + ox];
+            if (!PC && p.noise) nz = p.noise_w[0] * p.noise[(int64_t)img * p.noise_bstride + (int64_t)oy * p.Wo + ox];
             if (p.labels) {   // legacy-nearest lookup of the OUTPUT pixel (F.interpolate 'nearest', model.py:391)
                 const int sy = min((int)floorf((float)oy * ((float)p.Hm / (float)p.Ho)), p.Hm - 1);
                 const int sx = min((int)floorf((float)ox * ((float)p.Wm / (float)p.Wo)), p.Wm - 1);
@@ -873,24 +898,40 @@ __global__ __launch_bounds__(NTHR) void conv_bf16x3_region_kernel(const e4s_conv
     const float gain = (p.act == 1) ? p.gain : 1.f;
     const bool do_act = p.act != 0, scaled = p.out_scale != nullptr, raw = ksplit > 1;
     float* yo = raw ? p.splitk_ws + (size_t)ks * ((size_t)p.B * p.Ho * p.Wo * p.Cout) : p.y;
+    const float nw = PC ? p.noise_w[0] : 0.f;
+    const int hwo = p.Ho * p.Wo;
     // epilogue math per element, 4x4 transpose across each lane quad, one 16-byte store per (row, 4 columns): see the plain kernel
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             float v[TN][4];
+            float nzv[PC ? TN : 1][4];
+            if (PC && !raw) {
+                const int offn = s_out[(wm * TM + tm) * 32 + (li & 3) + 8 * g + 4 * kh];
+                // pixel of the noise map: bstride is 0 (one map for the batch) or Ho * Wo; a packed tile holds several images
+                const int64_t npix = p.noise_bstride ? (int64_t)offn : PACK ? (int64_t)(offn % hwo) : (int64_t)offn - (int64_t)tb * hwo;
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn) {
+                    f32x4 n4 = {0.f, 0.f, 0.f, 0.f};
+                    if (offn >= 0) n4 = *reinterpret_cast<const f32x4*>(p.noise + npix * p.Cout + n0 + (wn * TN + tn) * 32 + (li & ~3));
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) nzv[tn][e] = e4s_mul_rn(nw, n4[e]);
+                    quad_transpose4(nzv[tn][0], nzv[tn][1], nzv[tn][2], nzv[tn][3], li);
+                }
+            }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int r = 4 * g + i;
                 const int row = (wm * TM + tm) * 32 + i + 8 * g + 4 * kh;
-                const float nz = s_nz[row];
+                const float nz = PC ? 0.f : s_nz[row];
                 const float* drow = PACK ? p.out_scale + (size_t)s_grp[row] * p.Cout + n0 : sD + s_grp[row] * BN;     // PACK: d[image][region] per row
 #pragma unroll
                 for (int tn = 0; tn < TN; ++tn) {
                     const int ncol = (wn * TN + tn) * 32 + li;
                     float t = acc[tm][tn][r] * (scaled ? drow[ncol] : 1.f);
                     if (!raw) {
-                        t += nz + bsv[tn];
+                        t += (PC ? nzv[tn][i] : nz) + bsv[tn];
                         if (do_act) t = (t > 0.f ? t : t * p.alpha) * gain;
                     }
                     v[tn][i] = t;
@@ -919,10 +960,15 @@ int launch_region_v(const e4s_conv_params& p, const int* only_flagged, hipStream
     const bool pack = plan.path == 3;
     const int ksplit = plan.ksplit, cper = plan.cper;
     if (pack && only_flagged) return (int)hipErrorInvalidValue;           // packed launches have no rows kernel in front and no flag table
-    auto kern = pack ? conv_bf16x3_region_kernel<WN_, SPL, false, true>
+    const bool pc = e4s_noise_pc(p);
+    auto kern = pc ? (pack ? conv_bf16x3_region_kernel<WN_, SPL, false, true, true>
+                           : only_flagged ? conv_bf16x3_region_kernel<WN_, SPL, true, false, true>
+                                          : conv_bf16x3_region_kernel<WN_, SPL, false, false, true>)
+                   : pack ? conv_bf16x3_region_kernel<WN_, SPL, false, true>
                      : only_flagged ? conv_bf16x3_region_kernel<WN_, SPL, true> : conv_bf16x3_region_kernel<WN_, SPL, false>;
-    static std::atomic<uint64_t> smem_set[3] = {{0}, {0}, {0}};
-    if (int e = e4s_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM_REGION, smem_set[pack ? 2 : only_flagged ? 1 : 0])) return e;
+    static std::atomic<uint64_t> smem_set[6] = {{0}, {0}, {0}, {0}, {0}, {0}};
+    if (int e = e4s_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM_REGION,
+                                    smem_set[(pc ? 3 : 0) + (pack ? 2 : only_flagged ? 1 : 0)])) return e;
     const int ntn = p.Cout / BN;
     const e4s_few_tile::PackGeom geo = e4s_few_tile::pack_geom(p.Ha, p.Wa);
     // packed: tx_n = images per tile, one "tile per image" so that tt is the tile of the class
@@ -1277,6 +1323,32 @@ __global__ void splitk_epilogue_kernel(const e4s_conv_params p, const int ksplit
     *reinterpret_cast<f32x4*>(p.y + (size_t)pix * ycs + c) = v;
 }
 
+// the same with per-channel noise [Bn][hw][Cout]: the term is read with the slabs' own 16-byte pattern
+__global__ void splitk_epilogue_pc_kernel(const e4s_conv_params p, const int ksplit, const int ycs, const int64_t hw,
+                                          const int64_t n4) {
+    const int C4 = p.Cout / 4;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    const int c = (int)(i % C4) * 4;
+    const int64_t pix = i / C4;
+    const int64_t b = pix / hw;
+    const size_t slab = (size_t)p.B * hw * ycs;
+    const float* src = p.splitk_ws + (size_t)pix * ycs + c;
+    f32x4 v = *reinterpret_cast<const f32x4*>(src);
+    for (int k = 1; k < ksplit; ++k) v += *reinterpret_cast<const f32x4*>(src + (size_t)k * slab);
+    const f32x4 n4v = *reinterpret_cast<const f32x4*>(p.noise + (b * p.noise_bstride + (pix - b * hw)) * p.Cout + c);
+    const float nw = p.noise_w[0];
+    const float gain = (p.act == 1) ? p.gain : 1.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float nz = e4s_mul_rn(nw, n4v[e]);
+        float t = v[e] * (p.out_scale ? p.out_scale[b * p.Cout + c + e] : 1.f) + nz + (p.bias ? p.bias[c + e] : 0.f);
+        if (p.act) t = (t > 0.f ? t : t * (p.act == 2 ? p.slope[c + e] : p.alpha)) * gain;
+        v[e] = t;
+    }
+    *reinterpret_cast<f32x4*>(p.y + (size_t)pix * ycs + c) = v;
+}
+
 // the plain kernel's launch: the column tile by Cout (the polyphase up-conv is ONE GEMM with 4 Cout columns), few_tiles_split over its tiles
 e4s_plain_plan plain_plan(const e4s_conv_params& p) {
     e4s_plain_plan q;
@@ -1293,9 +1365,9 @@ e4s_plain_plan plain_plan(const e4s_conv_params& p) {
     return q;
 }
 
-template <typename C, int XF, bool SHUF, int VAR = 0>
+template <typename C, int XF, bool SHUF, int VAR = 0, bool PC = false>
 int launch(const e4s_conv_params& p, const e4s_plain_plan& plan, hipStream_t st) {
-    auto kern = conv_bf16x3_kernel<C, XF, SHUF, VAR>;
+    auto kern = conv_bf16x3_kernel<C, XF, SHUF, VAR, PC>;
     constexpr int SMEM = plain_smem<C, SHUF>();
     static_assert(SMEM <= 160 * 1024, "LDS budget");
     static std::atomic<uint64_t> smem_set{0};
@@ -1316,6 +1388,7 @@ int launch(const e4s_conv_params& p, const e4s_plain_plan& plan, hipStream_t st)
 template <typename C, bool SHUF>
 int launch_xf(const e4s_conv_params& p, const e4s_plain_plan& plan, hipStream_t st) {
     if (p.in_stats) return SHUF ? (int)hipErrorInvalidValue : launch<C, 2, false>(p, plan, st);
+    if (e4s_noise_pc(p)) return launch<C, 1, SHUF, 0, true>(p, plan, st);         // (styled layers: e4s_conv_bf16x3_f32 checked in_scale)
     return p.in_scale ? launch<C, 1, SHUF>(p, plan, st) : launch<C, 0, SHUF>(p, plan, st);
 }
 
@@ -1340,12 +1413,14 @@ extern "C" int e4s_conv_bf16x3_f32(const e4s_conv_params* pp, void* stream) {
         return launch_gather(p, as_stream(stream));
     }
     if (p.Cin % KC || p.Cout % 32 || p.ntaps != 9 || (p.ncls != 1 && !up) || p.istride != 1 ||
-        p.ostride != (up ? 2 : 1) || p.tiles || p.noise_per_channel || p.Ha != p.Hi || p.Wa != p.Wi ||
+        p.ostride != (up ? 2 : 1) || p.tiles || p.Ha != p.Hi || p.Wa != p.Wi ||
         p.Ho != p.Hi * p.ostride || p.Wo != p.Wi * p.ostride || (p.in_stats && p.in_scale))
         return (int)hipErrorInvalidValue;
     if (p.stats_ws && (p.labels || up || p.act != 0 || p.noise || p.out_scale ||
                        p.stats_slots != ((p.Ha + PTH - 1) / PTH) * ((p.Wa + TW - 1) / TW)))
         return (int)hipErrorInvalidValue;
+    if (e4s_noise_pc(p) && (!e4s_noise_pc_ok(p) || !p.in_scale || p.in_stats || (p.y_cstride && p.y_cstride % 4)))
+        return (int)hipErrorInvalidValue;           // per-channel noise: the styled layers of the generator (16-byte stores)
     hipStream_t st = as_stream(stream);
     if (p.labels) {                       // per-pixel regions: the region-select kernel (128-wide column tiles only)
         if (p.y_cstride || !p.in_scale || p.in_stats || p.act == 2 || p.Cout % BN || p.groups_per_batch < 1 || p.groups_per_batch > MAXR)
@@ -1387,6 +1462,10 @@ int e4s_splitk_epilogue(const e4s_conv_params& p, int ksplit, bool slabs_need_ou
     if (!slabs_need_out_scale) q.out_scale = nullptr;
     const int ycs = p.y_cstride ? p.y_cstride : p.Cout;
     const int64_t n4 = (int64_t)p.B * p.Ho * p.Wo * (p.Cout / 4);
+    if (e4s_noise_pc(p))
+        hipLaunchKernelGGL(splitk_epilogue_pc_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, q, ksplit, ycs,
+                           (int64_t)p.Ho * p.Wo, n4);
+    else
     hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, q, ksplit, ycs,
                        (int64_t)p.Ho * p.Wo, n4);
     E4S_CHECK_LAUNCH();

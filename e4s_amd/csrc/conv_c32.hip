@@ -38,8 +38,11 @@ static_assert(2 * SMEM <= 160 * 1024, "two blocks per CU");
 
 struct TileId { int tb, tyb, txb, nt; };
 
-// XF: 1 = v * in_scale[b][c] while the halo is staged; RGB: 1 = also emit the ToRGB partial (needs Cout == 32)
-template <int XF, int RGB>
+// XF: 1 = v * in_scale[b][c] while the halo is staged; RGB: 1 = also emit the ToRGB partial (needs Cout == 32); PC: 1 = per-channel
+// noise, NHWC [Bn][Ho][Wo][Cout]: after the MFMA loop the tile's noise_w * noise block is fetched with the output store's own access
+// pattern (16 bytes per lane, 8 lanes per pixel) into the staging tile, where each thread finds the terms of its accumulators
+// (fetched ahead of the loop, the 32 registers it occupies spilled; the co-resident block covers the latency)
+template <int XF, int RGB, int PC = 0>
 __global__ __launch_bounds__(NTHR, 2) void conv_c32_kernel(const e4s_conv_params p, const float* __restrict__ rgb_ws,
                                                            float* __restrict__ rgb_partial, const int ntn, const int tx_n,
                                                            const int per_img, const int ntiles, const int abl_arg) {
@@ -161,8 +164,8 @@ __global__ __launch_bounds__(NTHR, 2) void conv_c32_kernel(const e4s_conv_params
             const bool valid = ay < p.Ho && ax < p.Wo;
             s_out[tid] = valid ? (cur.tb * p.Ho + ay) * p.Wo + ax : -1;
             float nz = 0.f;
-            if (valid && p.noise) nz = p.noise_w[0] * p.noise[(int64_t)cur.tb * p.noise_bstride + (int64_t)ay * p.Wo + ax];
-            s_nz[tid] = nz;
+            if (!PC && valid && p.noise) nz = p.noise_w[0] * p.noise[(int64_t)cur.tb * p.noise_bstride + (int64_t)ay * p.Wo + ax];
+            if (!PC) s_nz[tid] = nz;
         }
         if (RGB && tid < 3 * BN) sWS[tid] = rgb_ws[(size_t)cur.tb * 3 * BN + tid];
         __syncthreads();
@@ -201,12 +204,27 @@ __global__ __launch_bounds__(NTHR, 2) void conv_c32_kernel(const e4s_conv_params
         const float gain = (p.act == 1) ? p.gain : 1.f;
         const int ycs = p.y_cstride ? p.y_cstride : p.Cout;
         __syncthreads();                                        // every wave is through with the halo: sY may overwrite it
+        if (PC) {                                               // pixel ps * 32 + (tid >> 3), channels 4 (tid & 7) .. + 3 of the n-tile
+            const float nw = p.noise_w[0];
+            const float* nb = p.noise + ((int64_t)cur.tb * p.noise_bstride - (int64_t)cur.tb * HWo) * p.Cout + cur.nt * BN + (tid & 7) * 4;
+#pragma unroll 4       // two batches of four 16-byte loads: all eight at once pushed this kernel (256 VGPRs, no headroom) into spills
+            for (int ps = 0; ps < BM / (NTHR / 8); ++ps) {
+                const int px = ps * (NTHR / 8) + (tid >> 3);
+                const int off = s_out[px];
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (off >= 0) v = *reinterpret_cast<const f32x4*>(nb + (int64_t)off * p.Cout);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = e4s_mul_rn(nw, v[e]);
+                *reinterpret_cast<f32x4*>(sY + px * YLD + (tid & 7) * 4) = v;
+            }
+            __syncthreads();
+        }
 #pragma unroll
         for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = wave * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                float v = acc[tm][r] * osc + s_nz[row] + bsv;
+                float v = acc[tm][r] * osc + (PC ? sY[row * YLD + li] : s_nz[row]) + bsv;       // (PC: read and re-written by this thread alone)
                 if (p.act) v = (v > 0.f ? v : v * p.alpha) * gain;
                 sY[row * YLD + li] = v;
             }
@@ -336,9 +354,9 @@ __global__ __launch_bounds__(256) void torgb_finish_kernel(const float* __restri
     }
 }
 
-template <int XF, int RGB>
+template <int XF, int RGB, int PC>
 int launch(const e4s_conv_params& p, const float* rgb_ws, float* rgb_partial, hipStream_t st) {
-    auto kern = conv_c32_kernel<XF, RGB>;
+    auto kern = conv_c32_kernel<XF, RGB, PC>;
     static std::atomic<uint64_t> smem_set{0};
     if (int e = e4s_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM, smem_set)) return e;
     const int ntn = p.Cout / BN;
@@ -360,18 +378,23 @@ int launch(const e4s_conv_params& p, const float* rgb_ws, float* rgb_partial, hi
 }  // namespace
 
 // p as e4s_conv_bf16x3_f32 (natural-order 3x3, stride 1, Cin == 32, Cout % 32 == 0, one style per sample or none, per-pixel
-// noise, bias, act 0/1); w = the split image of the tap-packed weights [9][Cout][32].  rgb_ws [B][3][32] + rgb_partial
+// noise [Bn][Ho][Wo] or, with noise_per_channel, [Bn][Ho][Wo][Cout] (16-byte aligned), bias, act 0/1); w = the split image of the tap-packed weights [9][Cout][32].  rgb_ws [B][3][32] + rgb_partial
 // [B][3][H][W] (both or neither; Cout == 32): also emit rgb_partial = ToRGB's 1x1 modulated conv of the layer's OUTPUT.
 extern "C" int e4s_conv_c32_bf16x3_f32(const e4s_conv_params* pp, const float* rgb_ws, float* rgb_partial, void* stream) {
     const e4s_conv_params& p = *pp;
     if (p.Cin != KC || p.Cout % BN || p.ntaps != 9 || p.ncls != 1 || p.istride != 1 || p.ostride != 1 || p.tiles || p.labels ||
-        p.in_stats || p.noise_per_channel || p.act == 2 || p.Ho != p.Hi || p.Wo != p.Wi || p.B <= 0 || p.stats_ws)
+        p.in_stats || p.act == 2 || p.Ho != p.Hi || p.Wo != p.Wi || p.B <= 0 || p.stats_ws)
         return (int)hipErrorInvalidValue;
     if ((rgb_ws == nullptr) != (rgb_partial == nullptr) || (rgb_ws && p.Cout != BN)) return (int)hipErrorInvalidValue;
     if ((int64_t)p.B * p.Ho * p.Wo >= (1ll << 31)) return (int)hipErrorInvalidValue;
     hipStream_t st = as_stream(stream);
-    if (p.in_scale) return rgb_ws ? launch<1, 1>(p, rgb_ws, rgb_partial, st) : launch<1, 0>(p, rgb_ws, rgb_partial, st);
-    return rgb_ws ? launch<0, 1>(p, rgb_ws, rgb_partial, st) : launch<0, 0>(p, rgb_ws, rgb_partial, st);
+    if (p.noise && p.noise_per_channel) {                     // the editor's noise: styled layers only (XF = 1)
+        if (!p.in_scale || !p.noise_w || !aligned16(p.noise) || (p.noise_bstride != 0 && p.noise_bstride != (int64_t)p.Ho * p.Wo))
+            return (int)hipErrorInvalidValue;
+        return rgb_ws ? launch<1, 1, 1>(p, rgb_ws, rgb_partial, st) : launch<1, 0, 1>(p, rgb_ws, rgb_partial, st);
+    }
+    if (p.in_scale) return rgb_ws ? launch<1, 1, 0>(p, rgb_ws, rgb_partial, st) : launch<1, 0, 0>(p, rgb_ws, rgb_partial, st);
+    return rgb_ws ? launch<0, 1, 0>(p, rgb_ws, rgb_partial, st) : launch<0, 0, 0>(p, rgb_ws, rgb_partial, st);
 }
 
 extern "C" int e4s_torgb_finish_f32(const float* partial, const float* bias, const float* skip, const float* k4, float* out, int B,

@@ -41,4 +41,9 @@ int e4s_launch_wino1w(const e4s_conv_params& p, int ntn, int tx_n, int per_img, 
 // second stage of every split-K launch (conv_bf16x3.hip): slabs p.splitk_ws[k] are added in order, then noise / bias / activation;
 // slabs_need_out_scale: the slabs are raw sums (the plain kernel's), not yet multiplied by p.out_scale
 int e4s_splitk_epilogue(const e4s_conv_params& p, int ksplit, bool slabs_need_out_scale, hipStream_t st);
+// per-channel noise (the editor's maps, NHWC [Bn][Ho][Wo][Cout]): every epilogue reads it 16 bytes at a time beside its output store
+inline bool e4s_noise_pc(const e4s_conv_params& p) { return p.noise != nullptr && p.noise_per_channel != 0; }
+inline bool e4s_noise_pc_ok(const e4s_conv_params& p) {
+    return p.noise_w && aligned16(p.noise) && p.Cout % 4 == 0 && (p.noise_bstride == 0 || p.noise_bstride == (int64_t)p.Ho * p.Wo);
+}
 int e4s_num_cus();             // CUs of the current device (256 if it cannot be asked): the grid of the persistent kernels (conv_bf16x3.hip)

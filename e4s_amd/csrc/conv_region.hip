@@ -41,6 +41,9 @@ constexpr int SMEM = OFF_TBL + TBL_BYTES;
 static_assert(SMEM <= 160 * 1024, "LDS budget");
 static_assert(MAXR * BN * 4 <= A_BYTES, "epilogue table");
 
+// PC: per-channel noise [Bn][Ho][Wo][Cout], read beside the output store (16 bytes per lane, the store's address pattern, back to the
+// accumulators' layout through the quad transpose) instead of the row table's term; a separate instantiation
+template <bool PC>
 __global__ __launch_bounds__(NTHR) void conv_region_rows_kernel(const e4s_conv_params p, const unsigned char* __restrict__ w16,
                                                                 int* __restrict__ tile_flags, const int ntn, const int tx_n,
                                                                 const int per_img, const int tiles_per_cls, const int ksplit,
@@ -105,7 +108,7 @@ __global__ __launch_bounds__(NTHR) void conv_region_rows_kernel(const e4s_conv_p
         float nz = 0.f;
         int r = 0;
         if (valid) {
-            if (p.noise) nz = p.noise_w[0] * p.noise[(int64_t)tb * p.noise_bstride + (int64_t)oy * p.Wo + ox];
+            if (!PC && p.noise) nz = p.noise_w[0] * p.noise[(int64_t)tb * p.noise_bstride + (int64_t)oy * p.Wo + ox];
             r = label_at(p, tb, oy, ox);
         }
         T.nz[tid] = nz;
@@ -264,23 +267,37 @@ __global__ __launch_bounds__(NTHR) void conv_region_rows_kernel(const e4s_conv_p
     const float gain = (p.act == 1) ? p.gain : 1.f;
     const bool do_act = p.act != 0, scaled = p.out_scale != nullptr, raw = ksplit > 1;
     float* yo = raw ? p.splitk_ws + (size_t)ks * ((size_t)p.B * p.Ho * p.Wo * p.Cout) : p.y;
+    const float nw = PC ? p.noise_w[0] : 0.f;
+    const float* nzb = PC ? p.noise + ((int64_t)tb * p.noise_bstride - (int64_t)tb * p.Ho * p.Wo) * p.Cout + n0 : nullptr;
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             float v[TN][4];
+            float nzv[PC ? TN : 1][4];
+            if (PC && !raw) {
+                const int offn = T.out[(wm * TM + tm) * 32 + (li & 3) + 8 * g + 4 * kh];
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn) {
+                    f32x4 n4 = {0.f, 0.f, 0.f, 0.f};
+                    if (offn >= 0) n4 = *reinterpret_cast<const f32x4*>(nzb + (int64_t)offn * p.Cout + (wn * TN + tn) * 32 + (li & ~3));
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) nzv[tn][e] = e4s_mul_rn(nw, n4[e]);
+                    quad_transpose4(nzv[tn][0], nzv[tn][1], nzv[tn][2], nzv[tn][3], li);
+                }
+            }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int r = 4 * g + i;
                 const int row = (wm * TM + tm) * 32 + i + 8 * g + 4 * kh;
-                const float nz = T.nz[row];
+                const float nz = PC ? 0.f : T.nz[row];
                 const float* drow = sD + T.grp[row] * BN;
 #pragma unroll
                 for (int tn = 0; tn < TN; ++tn) {
                     const int ncol = (wn * TN + tn) * 32 + li;
                     float t = acc[tm][tn][r] * (scaled ? drow[ncol] : 1.f);
                     if (!raw) {
-                        t += nz + bsv[tn];
+                        t += (PC ? nzv[tn][i] : nz) + bsv[tn];
                         if (do_act) t = (t > 0.f ? t : t * p.alpha) * gain;
                     }
                     v[tn][i] = t;
@@ -348,7 +365,7 @@ static bool region_rows_ok(const e4s_conv_params& p) {
     const bool up = (p.ncls == 4);
     return p.labels && p.in_scale && !p.in_stats && !p.y_cstride && p.act != 2 && p.Cin % 32 == 0 && p.Cout % BN == 0 &&
            p.ntaps == 9 && (p.ncls == 1 || up) && p.istride == 1 && p.ostride == (up ? 2 : 1) && !p.tiles &&
-           !p.noise_per_channel && p.Ha == p.Hi && p.Wa == p.Wi && p.Ho == p.Hi * p.ostride && p.Wo == p.Wi * p.ostride &&
+           (!e4s_noise_pc(p) || e4s_noise_pc_ok(p)) && p.Ha == p.Hi && p.Wa == p.Wi && p.Ho == p.Hi * p.ostride && p.Wo == p.Wi * p.ostride &&
            !p.stats_ws && p.groups_per_batch >= 1 && p.groups_per_batch <= MAXR &&
            (int64_t)p.Hi * p.Wi * p.Cin < (1ll << 31) && (int64_t)p.B * p.Ho * p.Wo < (1ll << 31);
 }
@@ -371,7 +388,9 @@ e4s_masked_plan e4s_plan_masked(const e4s_conv_params& p) {
         e4s_split::pack_split(e4s_few_tile::pack_tiles(e4s_few_tile::pack_geom(p.Ha, p.Wa), p.B) * ctiles, p.Cin / 32, m.ksplit, m.cper);
     } else {
         e4s_split::few_tiles_split(m.flag_ints * (p.Cout / BN), p.Cin / 32, m.ksplit, m.cper);
-        m.path = (region_1w_mode() && m.ksplit == 1 && e4s_region_rows1w_ok(p)) ? 2 : 1;
+        // per-channel noise stays on this file's 8-wave kernel: with the 16-byte noise reads in its epilogue the one-wave kernel (all 512
+        // registers of the SIMD in use) spilled two VGPRs
+        m.path = (region_1w_mode() && m.ksplit == 1 && !e4s_noise_pc(p) && e4s_region_rows1w_ok(p)) ? 2 : 1;
     }
     m.slab_floats = m.ksplit > 1 ? (int64_t)m.ksplit * p.B * p.Ho * p.Wo * p.Cout : 0;
     return m;
@@ -394,9 +413,10 @@ extern "C" int e4s_conv_region_bf16x3_f32(const e4s_conv_params* pp, const void*
     // small maps (4^2, 8^2) go straight to the region-select kernel's packed tiles: no rows kernel, no overflow scan
     if (!w16 || m.path == 3) return e4s_launch_region_select(p, nullptr, st);
     if (!p.splitk_ws) return (int)hipErrorInvalidValue;
-    auto kern = conv_region_rows_kernel;
-    static std::atomic<uint64_t> smem_set{0};
-    if (int e = e4s_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM, smem_set)) return e;
+    const bool pc = e4s_noise_pc(p);
+    auto kern = pc ? conv_region_rows_kernel<true> : conv_region_rows_kernel<false>;
+    static std::atomic<uint64_t> smem_set{0}, smem_set_pc{0};
+    if (int e = e4s_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM, pc ? smem_set_pc : smem_set)) return e;
     const int ntn = p.Cout / BN;
     const int tx_n = (p.Wa + TW - 1) / TW, per_img = ((p.Ha + TH - 1) / TH) * tx_n;
     const int tiles_per_cls = p.B * per_img;

@@ -69,7 +69,9 @@ __device__ __forceinline__ void split_store(unsigned char* dst, const f32x8 v) {
 struct TileId { int tb, ty, tx, nt; };
 
 // XF: 0 none, 1 v * in_scale[b][c] while the halo is staged (one style per sample: unmasked StyledConv, model.py:655-657)
-template <int XF>
+// PC: 1 = per-channel noise, NHWC [Bn][Ho][Wo][Cout]: read beside the output store, 16 bytes per lane at the store's own address
+// pattern (the row table s_nz is not written)
+template <int XF, int PC = 0>
 __global__ __launch_bounds__(NTHR, 2) void upconv_fused_kernel(const e4s_conv_params p, const float* __restrict__ k4, const int ntn,
                                                            const int tx_n, const int per_img, const int ntiles, const int abl_arg) {
     // abl (profiling builds only, -DE4S_ABLATIONS + env E4S_UPCONV3_ABL; results WRONG): 1 no MFMA stages, 2 no FIR / output stores,
@@ -286,7 +288,7 @@ __global__ __launch_bounds__(NTHR, 2) void upconv_fused_kernel(const e4s_conv_pa
             for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
         // epilogue operands of THIS tile, requested now so that their latency hides under the tile's MFMA stages
         float nz_reg[2] = {0.f, 0.f};
-        if (p.noise) {
+        if (!PC && p.noise) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int e = tid + NTHR * j;
@@ -331,7 +333,7 @@ __global__ __launch_bounds__(NTHR, 2) void upconv_fused_kernel(const e4s_conv_pa
         // ---- epilogue (a): accumulators -> I tile; anchor (ay, ax), class (dy, dx) -> I[2 ay + dy][2 ax + dx][co] ----
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-            if (tid + NTHR * j < NZ) s_nz[tid + NTHR * j] = nw_reg * nz_reg[j];      // (outside the aliased region)
+            if (!PC && tid + NTHR * j < NZ) s_nz[tid + NTHR * j] = nw_reg * nz_reg[j];      // (outside the aliased region)
         if (abl == 3 || abl == 7) asm volatile("" :: "v"(acc[0][0]), "v"(acc[1][7]), "v"(acc[2][3]), "v"(acc[3][9]));
         if (abl != 3 && abl != 7)
 #pragma unroll
@@ -357,6 +359,14 @@ __global__ __launch_bounds__(NTHR, 2) void upconv_fused_kernel(const e4s_conv_pa
             auto finish = [&](f32x4 v, int r) {
                 const int oy = cur.ty * OH + r;
                 if (oy < p.Ho && ox < p.Wo) {
+                    if (PC) {
+                        const f32x4 nz = *reinterpret_cast<const f32x4*>(
+                            p.noise + ((int64_t)cur.tb * p.noise_bstride + (int64_t)oy * p.Wo + ox) * p.Cout + co0);
+                        f32x4 nzw;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) nzw[e] = e4s_mul_rn(nw_reg, nz[e]);
+                        v = v * d + bs + nzw;
+                    } else
                     v = v * d + bs + s_nz[r * OW + e_ox];
                     if (p.act) {
 #pragma unroll
@@ -463,18 +473,22 @@ extern "C" int e4s_subpixel_weights_f32(const float* w, void* out, int Cout, int
 }
 
 // p: x NHWC [B,H,W,Cin], w = e4s_subpixel_weights_f32's output, y NHWC [B,2H,2W,Cout (or y_cstride)], in_scale [B,Cin] | null,
-// out_scale [B,Cout] | null, noise / noise_w / bias / act / alpha / gain as e4s_conv_bf16x3_f32; k4: DEVICE pointer to the 4x4
+// out_scale [B,Cout] | null, noise (per pixel, or per channel [Bn][Ho][Wo][Cout], 16-byte aligned) / noise_w / bias / act / alpha /
+// gain as e4s_conv_bf16x3_f32; k4: DEVICE pointer to the 4x4
 // blur kernel (model.py:206-213, already x4).
 extern "C" int e4s_upconv_bf16x3_f32(const e4s_conv_params* pp, const float* k4, void* stream) {
     const e4s_conv_params& p = *pp;
     // Cin % 32: the stage pipeline is unrolled by two 16-channel chunks
-    if (p.Cin % (2 * KC) || p.Cin > MAXC || p.Cout % BNC || !k4 || p.labels || p.tiles || p.in_stats || p.noise_per_channel || p.act == 2 ||
+    if (p.Cin % (2 * KC) || p.Cin > MAXC || p.Cout % BNC || !k4 || p.labels || p.tiles || p.in_stats || p.act == 2 ||
         p.Ho != 2 * p.Hi || p.Wo != 2 * p.Wi || p.B <= 0 || (p.y_cstride && p.y_cstride % 4))
         return (int)hipErrorInvalidValue;
     hipStream_t st = as_stream(stream);
-    auto kern = p.in_scale ? upconv_fused_kernel<1> : upconv_fused_kernel<0>;
-    static std::atomic<uint64_t> smem_set0{0}, smem_set1{0};
-    if (int e = e4s_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM, p.in_scale ? smem_set1 : smem_set0)) return e;
+    const bool pc = p.noise && p.noise_per_channel;            // the editor's noise [Bn][Ho][Wo][Cout]: styled layers only (XF = 1)
+    if (pc && (!p.in_scale || !p.noise_w || !aligned16(p.noise) || (p.noise_bstride != 0 && p.noise_bstride != (int64_t)p.Ho * p.Wo)))
+        return (int)hipErrorInvalidValue;
+    auto kern = pc ? upconv_fused_kernel<1, 1> : p.in_scale ? upconv_fused_kernel<1, 0> : upconv_fused_kernel<0, 0>;
+    static std::atomic<uint64_t> smem_set0{0}, smem_set1{0}, smem_set2{0};
+    if (int e = e4s_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM, pc ? smem_set2 : p.in_scale ? smem_set1 : smem_set0)) return e;
     const int ntn = p.Cout / BNC;
     const int tx_n = (p.Wo + OW - 1) / OW, per_img = ((p.Ho + OH - 1) / OH) * tx_n;
     const int64_t ntiles = (int64_t)p.B * per_img * ntn;

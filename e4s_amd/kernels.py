@@ -380,7 +380,8 @@ def conv_mfma(x, w, cout, *, plan=None, istride=1, ostride=1, ntaps=9, ncls=1, i
         if not gather_ok and (
                 not bf16x3_eligible(cin, cout, istride=istride, ostride=ostride, ntaps=ntaps, ncls=ncls,
                                     masked=labels is not None)
-                or not spatial or noise_per_channel or (labels is not None and in_scale is None)
+                or not spatial or (noise_per_channel and (in_scale is None or in_stats is not None))
+                or (labels is not None and in_scale is None)
                 or (in_stats is not None and (in_scale is not None or labels is not None))):
             raise RuntimeError("e4s_conv_bf16x3_f32 does not cover this contraction")
         p.w = fptr(w_split)
@@ -642,10 +643,11 @@ def upconv_bf16x3_eligible(cin, cout):
     return cin % 64 == 0 and cin <= 512 and cout % 32 == 0
 
 
-def upconv_bf16x3(x, w_sub, cout, k4, *, in_scale=None, out_scale=None, noise=None, noise_w=None, bias=None, act=0,
-                  alpha=0.2, gain=LRELU_GAIN, out=None):
+def upconv_bf16x3(x, w_sub, cout, k4, *, in_scale=None, out_scale=None, noise=None, noise_w=None, noise_per_channel=False, bias=None,
+                  act=0, alpha=0.2, gain=LRELU_GAIN, out=None):
     """Exact transposed conv + blur + noise + bias + act on the split-bf16 matrix-core path, one style per sample.
-    x NHWC [B,H,W,Cin]; w_sub = subpixel_weights(w); k4 the 4x4 blur kernel (device tensor) -> NHWC [B,2H,2W,Cout]."""
+    x NHWC [B,H,W,Cin]; w_sub = subpixel_weights(w); k4 the 4x4 blur kernel (device tensor) -> NHWC [B,2H,2W,Cout].
+    noise [1|B,1,2H,2W], or with noise_per_channel NHWC [1|B,2H,2W,Cout] (needs in_scale)."""
     b, hi, wi, cin = x.shape
     ho, wo = 2 * hi, 2 * wi
     y = torch.empty(b, ho, wo, cout, device=x.device, dtype=torch.float32) if out is None else out
@@ -666,18 +668,18 @@ def upconv_bf16x3(x, w_sub, cout, k4, *, in_scale=None, out_scale=None, noise=No
     else:
         p.noise = p.noise_w = None
         p.noise_bstride = 0
-    p.noise_per_channel = 0
+    p.noise_per_channel = 1 if (noise is not None and noise_per_channel) else 0
     p.bias, p.slope = fptr(bias), None
     p.act, p.alpha, p.gain = act, alpha, gain
     call("e4s_upconv_bf16x3_f32", ctypes.byref(p), fptr(_f32(k4)), stream())
     return y
 
 
-def conv_c32(x, w_split, cout, *, in_scale=None, out_scale=None, noise=None, noise_w=None, bias=None, act=0, alpha=0.2,
-             gain=LRELU_GAIN, rgb_ws=None):
+def conv_c32(x, w_split, cout, *, in_scale=None, out_scale=None, noise=None, noise_w=None, noise_per_channel=False, bias=None, act=0,
+             alpha=0.2, gain=LRELU_GAIN, rgb_ws=None):
     """3x3 stride-1 conv with 32 input channels on e4s_conv_c32_bf16x3_f32 (weights resident in LDS).  x NHWC [B,H,W,32];
     w_split = split_bf16x2(pack_taps(w)); rgb_ws [B,3,32]: also return the ToRGB partial [B,3,H,W] of the OUTPUT (Cout == 32).
-    Returns y NHWC [B,H,W,Cout] or (y, rgb_partial)."""
+    noise [1|B,1,H,W], or with noise_per_channel NHWC [1|B,H,W,Cout] (needs in_scale).  Returns y NHWC [B,H,W,Cout] or (y, rgb_partial)."""
     b, h, w, cin = x.shape
     if cin != 32 or cout % 32:
         raise RuntimeError("conv_c32: Cin == 32 and Cout % 32 == 0")
@@ -699,7 +701,7 @@ def conv_c32(x, w_split, cout, *, in_scale=None, out_scale=None, noise=None, noi
     else:
         p.noise = p.noise_w = None
         p.noise_bstride = 0
-    p.noise_per_channel = 0
+    p.noise_per_channel = 1 if (noise is not None and noise_per_channel) else 0
     p.bias, p.slope = fptr(bias), None
     p.act, p.alpha, p.gain = act, alpha, gain
     partial = None
@@ -2593,3 +2595,52 @@ def face_to_net(faces_u8, bgr=False, rgb=True, net=True, out_rgb=None, out_net=N
     o_net = _join_out(out_net, (b, 3, h, w), torch.float32, x, "face_to_net: out_net") if net or out_net is not None else None
     call("e4s_face_to_net_u8", ptr(x), 1 if bgr else 0, ptr(o_rgb), fptr(o_net), b, h, w, stream())
     return o_rgb, o_net
+
+
+# ---- face editing (edit.py; csrc/edit.hip) -----------------------------------------------------
+def texture_mix(src, ref, sel, a0, a1, out=None):
+    """scripts/face_edit.py:81-87 for a batch, one launch: out[b,r] = sel[b,r] ? a0[b,r] * src[b|0,r] + a1[b,r] * ref[b|0,r] : src[b|0,r]
+    (two products, one sum, a rounding each; unselected rows copied).  src / ref fp32 [1|B,R,C]; sel uint8, a0, a1 fp32 [B,R]."""
+    a0 = _join_arg(a0, "texture_mix: a0 is an fp32 [B,R] tensor", torch.float32, 2)
+    b, r = a0.shape
+    src = _join_arg(src, "texture_mix: src is an fp32 [1|B,R,C] tensor", torch.float32, 3)
+    ref = _join_arg(ref, "texture_mix: ref is an fp32 [1|B,R,C] tensor", torch.float32, 3)
+    a1 = _join_arg(a1, "texture_mix: a1 is an fp32 [B,R] tensor", torch.float32, 2)
+    sel = _join_arg(sel, "texture_mix: sel is a uint8 [B,R] tensor", torch.uint8, 2)
+    c = src.shape[2]
+    if (b < 1 or r < 1 or c < 1 or tuple(sel.shape) != (b, r) or tuple(a1.shape) != (b, r) or src.shape[0] not in (1, b)
+            or ref.shape[0] not in (1, b) or tuple(src.shape[1:]) != (r, c) or tuple(ref.shape[1:]) != (r, c)):
+        raise ValueError(f"texture_mix: src {tuple(src.shape)} / ref {tuple(ref.shape)} are [1|B,R,C] and sel {tuple(sel.shape)} / a0 "
+                         f"{tuple(a0.shape)} / a1 {tuple(a1.shape)} are [B,R]")
+    out = _join_out(out, (b, r, c), torch.float32, src, "texture_mix: out")
+    call("e4s_texture_mix_f32", fptr(src), fptr(ref), ptr(sel), fptr(a0), fptr(a1), fptr(out), b, r, c,
+         1 if src.shape[0] == 1 and b > 1 else 0, 1 if ref.shape[0] == 1 and b > 1 else 0, stream())
+    return out
+
+
+def labels_to_color(labels, out=None):
+    """demo/gradio_utils.py:58-73: uint8 label maps [...] -> uint8 RGB [...,3] in the demo's 19 colours; ids >= 19 black."""
+    x = _join_arg(labels, "labels_to_color: a uint8 label map", torch.uint8, labels.dim() if isinstance(labels, torch.Tensor) else 0)
+    out = _join_out(out, tuple(x.shape) + (3,), torch.uint8, x, "labels_to_color: out")
+    call("e4s_labels_to_color_u8", ptr(x), ptr(out), x.numel(), stream())
+    return out
+
+
+def color_to_labels(rgb, out=None):
+    """demo/gradio_utils.py:75-84: uint8 RGB [...,3] -> uint8 label maps [...]; colours outside the table 0."""
+    x = _join_arg(rgb, "color_to_labels: a uint8 RGB map [...,3]", torch.uint8, rgb.dim() if isinstance(rgb, torch.Tensor) else 0, 3)
+    out = _join_out(out, tuple(x.shape[:-1]), torch.uint8, x, "color_to_labels: out")
+    call("e4s_color_to_labels_u8", ptr(x), ptr(out), out.numel(), stream())
+    return out
+
+
+def mask_brush(labels, brush, comp_idx, out=None):
+    """demo/gradio_demo.py:126-130: labels[sum(brush[..., :3]) != 0] = comp_idx.  labels uint8 [...], brush uint8 [...,3|4] (gradio's
+    sketch is RGBA); out may be labels (in place)."""
+    x = _join_arg(labels, "mask_brush: a uint8 label map", torch.uint8, labels.dim() if isinstance(labels, torch.Tensor) else 0)
+    br = _join_arg(brush, "mask_brush: a uint8 brush [...,3|4]", torch.uint8, x.dim() + 1)
+    if br.shape[-1] not in (3, 4) or tuple(br.shape[:-1]) != tuple(x.shape) or not 0 <= int(comp_idx) <= 255:
+        raise ValueError(f"mask_brush: brush {tuple(br.shape)} is the label map's shape {tuple(x.shape)} + (3|4,), comp_idx a byte")
+    out = _join_out(out, tuple(x.shape), torch.uint8, x, "mask_brush: out")
+    call("e4s_mask_brush_u8", ptr(x), ptr(br), ptr(out), x.numel(), int(br.shape[-1]), int(comp_idx), stream())
+    return out

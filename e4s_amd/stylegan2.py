@@ -43,6 +43,9 @@ UPCONV_BF16X3_EXACT = os.environ.get("E4S_UPCONV_BF16X3", "exact") != "polyphase
 CONV_C32 = os.environ.get("E4S_CONV_C32", "1") != "0"
 # masked layers on the variant-rows kernel (csrc/conv_region.hip); "0": the region-select kernel of conv_bf16x3.hip everywhere
 REGION_ROWS = os.environ.get("E4S_REGION_ROWS", "1") != "0"
+# per-channel noise maps [1|B,C,H,W] (the face editor's, e4s_amd/edit.py) in the epilogues of the split-bf16 kernels; "0": such layers run
+# the exact-fp32 kernels whatever E4S_PRECISION says, as they did before those epilogues could read the layout
+PC_NOISE_SPLIT = os.environ.get("E4S_PC_NOISE_SPLIT", "1") != "0"
 
 
 def make_kernel(k):
@@ -318,7 +321,10 @@ def _prep_noise(noise, b, h, w, device):
         raise RuntimeError(f"noise of shape {tuple(noise.shape)} is not broadcastable to [{b},C,{h},{w}]")
     if noise.shape[1] == 1:
         return noise.contiguous(), False
-    return K.nchw_to_nhwc(noise), True           # [1,C,H,W] noise of scripts/face_edit.py:49-52
+    nhwc = noise.permute(0, 2, 3, 1)             # [1,C,H,W] noise of scripts/face_edit.py:49-52
+    if nhwc.is_contiguous():                     # stored channels-last (edit.make_noise): the layout the epilogues read, a view
+        return nhwc, True
+    return K.nchw_to_nhwc(noise), True
 
 
 class StyledConv(nn.Module):
@@ -356,26 +362,27 @@ class StyledConv(nn.Module):
                 raise NotImplementedError("backward with per-channel noise maps")
             rec.update(d=d, noise=nz)
         ncls = 4 if conv.upsample else 1
-        if not per_ch and self.c32_eligible(b, h, w, labels, plan):
+        split_ok = not per_ch or PC_NOISE_SPLIT      # per-channel noise (the editor's) on the split-bf16 kernels' epilogues
+        if split_ok and self.c32_eligible(b, h, w, labels, plan):
             return K.conv_c32(x, conv.split_weights(), conv.out_channel, in_scale=s, out_scale=d, noise=nz,
-                              noise_w=self.noise.weight, bias=self.activate.bias, act=1, alpha=self.activate.negative_slope,
+                              noise_w=self.noise.weight, noise_per_channel=per_ch, bias=self.activate.bias, act=1, alpha=self.activate.negative_slope,
                               gain=self.activate.scale, rgb_ws=rgb_ws)
         if rgb_ws is not None:
             raise RuntimeError("the fused ToRGB partial exists only on the Cin == 32 kernel")
-        if (conv.upsample and labels is None and plan is None and not per_ch and UPCONV_BF16X3_EXACT
+        if (conv.upsample and labels is None and plan is None and split_ok and UPCONV_BF16X3_EXACT
                 and K.upconv_bf16x3_eligible(conv.in_channel, conv.out_channel)
                 and K.want_bf16x3(b, h, w, conv.in_channel, conv.out_channel, ncls, masked=False)):
             # unmasked up-conv: the exact transposed conv as a sub-pixel GEMM on the split-bf16 path (9 Cin Cout MACs per
             # input pixel instead of the polyphase form's 36) + one FIR / noise / bias / activation pass
             return K.upconv_bf16x3(x, conv.subpixel_split_weights(), conv.out_channel, conv.blur.kernel, in_scale=s,
-                                   out_scale=d, noise=nz, noise_w=self.noise.weight, bias=self.activate.bias, act=1,
-                                   alpha=self.activate.negative_slope, gain=self.activate.scale)
-        if plan is None and not per_ch and K.want_bf16x3(b, h, w, conv.in_channel, conv.out_channel, ncls,
+                                   out_scale=d, noise=nz, noise_w=self.noise.weight, noise_per_channel=per_ch,
+                                   bias=self.activate.bias, act=1, alpha=self.activate.negative_slope, gain=self.activate.scale)
+        if plan is None and split_ok and K.want_bf16x3(b, h, w, conv.in_channel, conv.out_channel, ncls,
                                                          masked=labels is not None):
             # split-bf16 matrix-core path (polyphase form for up-convs: 4x the MACs of the exact kernel at > 3x its rate)
             return K.conv_mfma(x, pk["w"], conv.out_channel, labels=labels, num_regions=num_regions, ncls=ncls,
                                ostride=2 if conv.upsample else 1, in_scale=s, out_scale=d, noise=nz,
-                               noise_w=self.noise.weight, bias=self.activate.bias, act=1,
+                               noise_w=self.noise.weight, noise_per_channel=per_ch, bias=self.activate.bias, act=1,
                                alpha=self.activate.negative_slope, gain=self.activate.scale,
                                w_split=conv.split_weights(),
                                w_split16=conv.split_weights16() if (labels is not None and REGION_ROWS) else None)
@@ -735,7 +742,7 @@ class Generator(nn.Module):
                     tape[-1]["is_feats"] = True
             nz2 = noise[i + 1]
             if (not soft and not conv2.mask_op and not to_rgb.mask_op and conv2.conv.out_channel == 32
-                    and (nz2 is None or nz2.shape[1] == 1) and conv2.c32_eligible(b, x.shape[1], x.shape[2])):
+                    and (nz2 is None or nz2.shape[1] == 1 or PC_NOISE_SPLIT) and conv2.c32_eligible(b, x.shape[1], x.shape[2])):
                 x, skip = styled_then_rgb(conv2, to_rgb, x, i + 1, nz2, skip)
             else:
                 x = styled(conv2, x, i + 1, nz2)

@@ -194,7 +194,7 @@ int e4s_upconv_blocks_per_cu(void);    /* diagnostic: occupancy of that kernel a
 /* Split-bf16 ("bf16x3") variant of the natural-order 3x3 stride-1 contraction: every fp32 operand v = hi + lo (two bf16),
  * product = a_hi*b_hi + a_hi*b_lo + a_lo*b_hi on v_mfma_f32_32x32x16_bf16 with an fp32 accumulator (relative error per
  * product <= ~2^-16; 5.3x the fp32-MFMA rate).  Same params struct and epilogue as e4s_conv_mfma_f32(spatial = 1) with:
- * ntaps = 9, istride = 1, noise_per_channel = 0, Cin % 32 == 0, Cout % 32 == 0, and p->w pointing at the SPLIT weights
+ * ntaps = 9, istride = 1, Cin % 32 == 0, Cout % 32 == 0, and p->w pointing at the SPLIT weights
  * produced by e4s_split_bf16x2_f32 from the tap-packed fp32 weights ([9][Cout][Cin], or the polyphase [4][9][Cout][Cin]
  * with ncls = 4, ostride = 2).  Variants:
  *   labels == NULL  one style per sample at most (in_scale/out_scale [B][C]) or in_stats (fused InstanceNorm): the
@@ -202,6 +202,10 @@ int e4s_upconv_blocks_per_cu(void);    /* diagnostic: occupancy of that kernel a
  *                   up-convs (model.py:655-657); column tile 128 / 64 / 32 by Cout
  *   labels != NULL  region-select (per-pixel style on the A fragment): masked StyledConvs (model.py:386-400), plain or
  *                   polyphase; Cout % 128 == 0, in_scale required, act != 2
+ * noise_per_channel (ABI v29; the face editor's maps, NHWC [Bn][Ho][Wo][Cout], 16-byte aligned, noise_bstride 0 or Ho * Wo) is taken by the
+ * styled launches (in_scale != NULL, no in_stats, y_cstride % 4 == 0), masked or not, with or without a K split: separate instantiations
+ * whose epilogues read the map 16 bytes per lane beside the output store.  act(d * acc + fl(noise_w * noise) + bias) * gain: the product
+ * is rounded on its own, as the per-pixel term is, so channel copies of one [Bn][Ho][Wo] map give that map's bits.
  * Strided (istride = 2, 3x3) and 1x1 launches run the per-tap gather kernel; a 3x3 launch of <= 64 tiles (256 pixels x 128 columns)
  * with Cin >= 256 splits its input channels over blocks: e4s_conv_bf16x3_ws_floats(p) > 0, p->splitk_ws required, p->stats_ws not allowed. */
 int e4s_conv_bf16x3_f32(const e4s_conv_params* p, void* stream);
@@ -236,7 +240,8 @@ int e4s_split_bf16x2_f32(const float* w, void* out, int64_t rows, int cin, void*
  * kernel (csrc/conv_region1w.hip: 256 x 256 tiles, 16 accumulator tiles per wave; Cout % 256 == 0 and no K split), 3 the region-select
  * kernel's packed tiles (maps small enough that a 256-row tile holds >= 2 whole images, csrc/few_tile_geom.h: 9 images at 4x4, 3 at 8x8;
  * K split down to one 32-channel chunk per block; no rows kernel and no overflow scan, with or without w16; E4S_REGION_PACK=0 in the
- * environment restores paths 1 / 2 for them). */
+ * environment restores paths 1 / 2 for them).  Launches with noise_per_channel (ABI v29) never take path 2: where a per-pixel launch would,
+ * they run path 1 without a K split. */
 int e4s_conv_region_bf16x3_f32(const e4s_conv_params* p, const void* w16, void* stream);
 int64_t e4s_conv_region_ws_floats(const e4s_conv_params* p);
 int e4s_conv_region_path(const e4s_conv_params* p);
@@ -502,14 +507,14 @@ int e4s_conv_wino_bf16x3_f32(const e4s_conv_params* p, void* stream);
  * Blur (src/models/stylegan2/model.py:287-300, 206-213) + NoiseInjection + FusedLeakyReLU (:396-404) in one kernel, one style
  * per sample (unmasked layers, model.py:655-657); Cin % 32 == 0, Cout % 32 == 0.
  * e4s_subpixel_weights_f32: w [Cout,Cin,3,3] -> the kernel's packed, hi/lo-split operand (9 * Cout * Cin * 4 bytes, opaque).
- * p: x / y NHWC, w = that buffer, in_scale [B,Cin] | NULL, out_scale [B,Cout] | NULL, noise / bias / act / alpha / gain as
- * e4s_conv_bf16x3_f32; k4: DEVICE pointer to the 4x4 blur taps. */
+ * p: x / y NHWC, w = that buffer, in_scale [B,Cin] | NULL, out_scale [B,Cout] | NULL, noise (per pixel, or with noise_per_channel
+ * and in_scale [Bn][Ho][Wo][Cout]) / bias / act / alpha / gain as e4s_conv_bf16x3_f32; k4: DEVICE pointer to the 4x4 blur taps. */
 int e4s_subpixel_weights_f32(const float* w, void* out, int Cout, int Cin, void* stream);
 int e4s_upconv_bf16x3_f32(const e4s_conv_params* p, const float* k4, void* stream);
 
 /* 3x3 stride-1 conv with Cin == 32 on the split-bf16 path, weights resident in LDS, halos fetched two tiles ahead
  * (csrc/conv_c32.hip): the generator's 32 -> 32 StyledConv at 1024^2 (model.py:537-549).  p as e4s_conv_bf16x3_f32 (no
- * labels / stats / split-K); w = split image of the tap-packed weights.  rgb_ws [B][3][32] and rgb_partial [B][3][H][W], both
+ * labels / stats / split-K; noise_per_channel needs in_scale); w = split image of the tap-packed weights.  rgb_ws [B][3][32] and rgb_partial [B][3][H][W], both
  * or neither (Cout == 32): the ToRGB 1x1 modulated conv (model.py:422-440) of the layer's output leaves the same pass;
  * e4s_torgb_finish_f32 then adds bias + the FIR-upsampled skip (model.py:441-446) -> out NCHW [B,3,H,W]. */
 int e4s_conv_c32_bf16x3_f32(const e4s_conv_params* p, const float* rgb_ws, float* rgb_partial, void* stream);
@@ -1096,6 +1101,22 @@ int e4s_driven_seam_f32(const float* pred, uint8_t* out_u8, uint8_t* enlarged_u8
 /* src uint8 [B,H,W,3], RGB or (bgr = 1) BGR -> rgb_u8 uint8 RGB [B,H,W,3] and net_f32 fp32 [B,3,H,W] = (v / 255 - 0.5) / 0.5 of the
  * RGB planes, in fp32 in this order (torchvision's ToTensor + Normalize(0.5, 0.5)).  Either output may be NULL, not both. */
 int e4s_face_to_net_u8(const uint8_t* src, int bgr, uint8_t* rgb_u8, float* net_f32, int B, int H, int W, void* stream);
+
+/* ---- face editing (e4s_amd/edit.py; csrc/edit.hip) ----
+ * The texture blend of scripts/face_edit.py:81-87 / demo/gradio_demo.py:165-170 for B samples of R regions in one launch:
+ *   out[b,r,:] = sel[b,r] ? fl(a0[b,r] * src[b,r,:]) + fl(a1[b,r] * ref[b,r,:]) : src[b,r,:]
+ * two products and one sum, one fp32 rounding each (never fused); unselected rows are copied bit for bit.  src, ref, out fp32
+ * [B,R,C]; src_b1 / ref_b1 = 1: that operand is [1,R,C], shared by the batch.  sel uint8 [B,R], a0, a1 fp32 [B,R], all on the
+ * device (a0 = float(1 - alpha) with the difference taken in double, a1 = float(alpha): what torch's scalar products compute). */
+int e4s_texture_mix_f32(const float* src, const float* ref, const uint8_t* sel, const float* a0, const float* a1, float* out, int B,
+                        int R, int C, int src_b1, int ref_b1, void* stream);
+/* demo/gradio_utils.py:58-84 on n pixels: labels uint8 [n] <-> rgb uint8 [n,3] over the demo's 19 colours.  To colour: ids >= 19
+ * (255 among them) are black.  To labels: exact RGB match, anything else 0. */
+int e4s_labels_to_color_u8(const uint8_t* labels, uint8_t* rgb, int64_t n, void* stream);
+int e4s_color_to_labels_u8(const uint8_t* rgb, uint8_t* labels, int64_t n, void* stream);
+/* demo/gradio_demo.py:126-130: out[i] = (brush[i][0] + brush[i][1] + brush[i][2] != 0) ? comp_idx : labels[i]; brush uint8
+ * [n,brush_pix], brush_pix 3 (RGB) or 4 (RGBA, alpha ignored); out may be labels. */
+int e4s_mask_brush_u8(const uint8_t* labels, const uint8_t* brush, uint8_t* out, int64_t n, int brush_pix, int comp_idx, void* stream);
 
 #ifdef __cplusplus
 }
