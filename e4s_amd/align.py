@@ -10,15 +10,16 @@ bit-identical to live Pillow).  The small host-side geometry (`compute_quad`, `c
 
 Out of scope:
   * landmark detection (dlib / face_alignment): the feature starts from 68 landmarks or from a quad, as crop_faces_by_quads does;
-  * crop_image's `shrink` branch (a quad diagonal of 4 x size or more: it needs Image.ANTIALIAS, which current Pillow no longer has)
-    and its `enable_padding` branch (the pipeline never passes it): NotImplementedError;
+  * crop_image's `enable_padding` branch (the pipeline never passes it): NotImplementedError.  Its `shrink` branch (a quad diagonal
+    of 4 x size or more) is opt-in, `crop_faces_by_quads(shrink=True)`: the frame is resized with LANCZOS (Image.ANTIALIAS under its
+    old name, which current Pillow no longer has) by `resize.pil_resize`; `crop_window` itself keeps refusing it;
   * paste_image_mask with a soft alpha (face_swap.py:52-72): Pillow warps RGBA premultiplied there, a different arithmetic, and the
     pipeline never calls it;
-  * the `src/` overlay: `src.utils.alignmengt` keeps executing the reference module in place;
-  * temporal smoothing of quads (crop_faces' center_sigma / xy_sigma)."""
+  * the `src/` overlay: `src.utils.alignmengt` keeps executing the reference module in place."""
 import numpy as np
 import torch
 
+from . import resize
 from .lib import call, fptr, ptr, stream
 
 
@@ -31,6 +32,12 @@ def compute_quad(lm68, scale=1.0):
         return np.stack([compute_quad(one, scale) for one in lm])
     if lm.shape != (68, 2):
         raise ValueError(f"compute_quad expects [68,2] or [B,68,2] landmarks, got {lm.shape}")
+    c, x, y = _transform(lm, scale)
+    return np.stack([c - x - y, c - x + y, c + x + y, c + x - y])
+
+
+def _transform(lm, scale):
+    """compute_transform's (c, x, y) of one [68,2] float64 landmark set."""
     eye_left = np.mean(lm[36:42], axis=0)
     eye_right = np.mean(lm[42:48], axis=0)
     eye_avg = (eye_left + eye_right) * 0.5
@@ -43,7 +50,41 @@ def compute_quad(lm68, scale=1.0):
     x *= scale
     y = np.flipud(x) * [-1, 1]
     c = eye_avg + eye_to_mouth * 0.1
-    return np.stack([c - x - y, c - x + y, c + x + y, c + x - y])
+    return c, x, y
+
+
+def gaussian_filter1d(a, sigma):
+    """scipy.ndimage.gaussian_filter1d(a, sigma, axis=0) with its defaults, in numpy: radius int(4 sigma + 0.5), taps
+    exp(-0.5 i^2 / sigma^2) normalised, boundary 'reflect' (d c b a | a b c d | d c b a, repeated as often as the radius needs);
+    summed as scipy's symmetric correlation does, the centre first and then the pairs from the outside in."""
+    a = np.asarray(a, dtype=np.float64)
+    sigma = float(sigma)
+    r = int(4.0 * sigma + 0.5)
+    i = np.arange(-r, r + 1)
+    taps = np.exp(-0.5 / (sigma * sigma) * i ** 2)
+    taps = taps / taps.sum()
+    n = a.shape[0]
+    p = np.pad(a, [(r, r)] + [(0, 0)] * (a.ndim - 1), mode="symmetric")
+    out = p[r:r + n] * taps[r]
+    for j in range(-r, 0):
+        out = out + (p[r + j:r + j + n] + p[r - j:r - j + n]) * taps[j + r]
+    return out
+
+
+def compute_quads(lm68, scale=1.0, center_sigma=0.0, xy_sigma=0.0):
+    """src/utils/alignmengt.py:191-210, crop_faces on given landmarks: lm68 [N,68,2] of N consecutive frames -> quads [N,4,2]
+    (float64), the centres smoothed over the frame axis with center_sigma and the half-axes with xy_sigma where that sigma is not
+    0.  With both 0 it is `compute_quad` of every frame."""
+    lm = np.asarray(lm68, dtype=np.float64)
+    if lm.ndim != 3 or lm.shape[1:] != (68, 2) or len(lm) == 0:
+        raise ValueError(f"compute_quads expects [N,68,2] landmarks, got {lm.shape}")
+    cs, xs, ys = (np.stack(v) for v in zip(*(_transform(one, scale) for one in lm)))
+    if center_sigma != 0:
+        cs = gaussian_filter1d(cs, center_sigma)
+    if xy_sigma != 0:
+        xs = gaussian_filter1d(xs, xy_sigma)
+        ys = gaussian_filter1d(ys, xy_sigma)
+    return np.stack([cs - xs - ys, cs - xs + ys, cs + xs + ys, cs + xs - ys], axis=1)
 
 
 def calc_alignment_coefficients(pa, pb):
@@ -91,6 +132,24 @@ def crop_window(quad, frame_hw, size=1024, enable_padding=False):
     if crop[2] - crop[0] < w or crop[3] - crop[1] < h:
         return crop
     return (0, 0, w, h)
+
+
+def crop_plan(quad, frame_hw, size=1024):
+    """crop_image up to its transform, shrink branch included (src/utils/alignmengt.py:97-121), for one quad in an H x W frame ->
+    (shrink, rsize, window, quad_in_window): shrink = floor(qsize / size * 0.5); above 1 the frame is resized to rsize = (width,
+    height) = rint(W / shrink), rint(H / shrink) with LANCZOS and the quad divided by shrink; window = (x0, y0, x1, y1) is what is
+    cut out of that (shrunk) frame, as `crop_window` finds it; quad_in_window is the (shrunk) quad relative to the window's origin
+    (Pillow gets it + 0.5).  With shrink <= 1, rsize is (W, H) and nothing is resized."""
+    quad = np.array(quad, dtype=np.float64).reshape(4, 2)
+    h, w = int(frame_hw[0]), int(frame_hw[1])
+    qsize = np.hypot(*((quad[3] - quad[1]) / 2)) * 2
+    shrink = int(np.floor(qsize / size * 0.5))
+    rsize = (w, h)
+    if shrink > 1:
+        rsize = (int(np.rint(float(w) / shrink)), int(np.rint(float(h) / shrink)))
+        quad /= shrink
+    window = crop_window(quad, (rsize[1], rsize[0]), size)          # (q / floor(q) < 2: the shrunk quad is below the threshold)
+    return shrink, rsize, window, quad - np.array(window[:2], dtype=np.float64)
 
 
 def crop_parameters(quads, frame_hw, size=1024):
@@ -162,17 +221,37 @@ def crop_faces_by_coeffs(frames_u8, coeffs, windows, size=1024, normalized=False
     return (out, norm) if norm is not None else out
 
 
-def crop_faces_by_quads(frames_u8, quads, size=1024, normalized=False):
+def crop_faces_by_quads(frames_u8, quads, size=1024, normalized=False, shrink=False, taps=None):
     """src/utils/alignmengt.py:217-225 for frames on the device: frames uint8 [B,H,W,3], quads [B,4,2] as the reference passes them
     (the + 0.5 is applied inside) -> aligned faces uint8 [B,size,size,3]; normalized=True: also the encoder's input, fp32
-    [B,3,size,size] = (face / 255 - 0.5) / 0.5 (the reference's ToTensor + Normalize), written in the same pass."""
+    [B,3,size,size] = (face / 255 - 0.5) / 0.5 (the reference's ToTensor + Normalize), written in the same pass.
+    shrink=True: a quad whose diagonal is 4 x size or more takes crop_image's shrink branch (`crop_plan`) where the default
+    refuses it: only the crop window of the LANCZOS-shrunk frame is made (`resize.pil_resize(window=...)`) and the crop kernel reads
+    that buffer.  taps: a dict that receives taps['shrunk'] = [(index, shrink, window, the uint8 [h,w,3] window), ...]."""
     frames = _images(frames_u8, "frames")
     quads = _quads(quads)
     if len(quads) != frames.shape[0]:
         raise RuntimeError(f"{len(quads)} quads for {frames.shape[0]} frames")
-    coeffs, windows = crop_parameters(quads, frames.shape[1:3], size)
-    return crop_faces_by_coeffs(frames, _to_device(coeffs, torch.float64, frames.device),
-                                _to_device(windows, torch.int32, frames.device), size, normalized)
+    dev = frames.device
+    plans = [crop_plan(q, frames.shape[1:3], size) for q in quads] if shrink else []
+    if not any(p[0] > 1 for p in plans):
+        coeffs, windows = crop_parameters(quads, frames.shape[1:3], size)
+        return crop_faces_by_coeffs(frames, _to_device(coeffs, torch.float64, dev), _to_device(windows, torch.int32, dev), size, normalized)
+    # faces of one call may shrink differently: one crop launch per face (a handful at most), each on its own frame or window
+    b = len(quads)
+    out = torch.empty(b, size, size, 3, device=dev, dtype=torch.uint8)
+    norm = torch.empty(b, 3, size, size, device=dev) if normalized else None
+    for i, (factor, rsize, win, quad) in enumerate(plans):
+        image, origin = frames[i:i + 1], win
+        if factor > 1:
+            image = resize.pil_resize(frames[i:i + 1], rsize, resize.LANCZOS, window=win)
+            origin = (0, 0, win[2] - win[0], win[3] - win[1])
+            if taps is not None:
+                taps.setdefault("shrunk", []).append((i, factor, win, image[0]))
+        coeffs = quad_coefficients(quad + 0.5, size)[None]
+        crop_faces_by_coeffs(image, _to_device(coeffs, torch.float64, dev), _to_device(np.array([origin]), torch.int32, dev), size,
+                             out=out[i:i + 1], out_normalized=None if norm is None else norm[i:i + 1])
+    return (out, norm) if norm is not None else out
 
 
 def paste_back_by_coeffs(faces_u8, frames_u8, coeffs, out=None):

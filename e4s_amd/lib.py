@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E4S_LIB_PATH") or os.path.join(_HERE, "libe4s_hip.so")      # (E4S_LIB_PATH: A/B runs of two builds)
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -378,6 +378,8 @@ SIGNATURES = {
     "e4s_labels_to_color_u8": [c_p, c_p, c_l, c_p],
     "e4s_color_to_labels_u8": [c_p, c_p, c_l, c_p],
     "e4s_mask_brush_u8": [c_p, c_p, c_p, c_l, c_i, c_i, c_p],
+    "e4s_pil_resample_h_u8": [c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_l, c_i, c_i, c_i, c_p],
+    "e4s_pil_resample_v_u8": [c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p],
 }
 
 INT64_RETURN = {"e4s_split16_bytes", "e4s_gather_frag_bytes", "e4s_instnorm_ws_doubles", "e4s_conv_bwd_ws_floats", "e4s_grouped_linear_t_ws_floats", "e4s_reduce_parts_ws_floats", "e4s_instnorm_bwd_ws_doubles", "e4s_prelu_bwd_ws_floats", "e4s_conv_wgrad_ws_floats", "e4s_conv_bf16x3_ws_floats", "e4s_conv_region_ws_floats", "e4s_lpips_layer_ws_doubles", "e4s_conv_mfma_ws_floats",

@@ -22,12 +22,13 @@ boxes (FaceRestorer.process, one device-to-host copy per frame):
     13  :313-327  PERSPECTIVE transform + alpha_composite           align.swap_into_frames
 
 Landmarks stay the caller's business (align.compute_quad(lm68) makes the quad crop_faces_by_quads takes): dlib and face_alignment
-are not part of the reference tree.  PIL's resize of un-cropped frames, SegNeXt parsing and FaceRestorer(in_size != out_size) are
-outside."""
+are not part of the reference tree; align.compute_quads adds crop_faces' temporal smoothing for a video.  PIL's resize of un-cropped
+frames to 1024 x 1024 (face_swap.py:184,190-191, BICUBIC) and crop_image's shrink branch for close-ups in large frames are opt-in,
+FaceSwapPipeline(any_size=True), both through resize.pil_resize.  SegNeXt parsing and FaceRestorer(in_size != out_size) are outside."""
 import numpy as np
 import torch
 
-from . import align, postproc
+from . import align, postproc, resize
 from . import kernels as K
 from .networks import GraphedFaceSwap, face_swap_core
 
@@ -69,9 +70,13 @@ class FaceSwapPipeline(object):
     parser     .parse(uint8 RGB [B,1024,1024,3]) -> uint8 labels [B,512,512] of the 12 E4S classes        (face_parser.FaceParser)
     batch      the swap's batch: with graph=True a GraphedFaceSwap(net, batch) is captured on first use and replayed per chunk of
                `batch` targets, the join kernels writing its static inputs in place; a final partial chunk runs eagerly
-    noise      the generator's noise maps as face_swap_core takes them; default: drawn once, here, with a fixed seed."""
+    noise      the generator's noise maps as face_swap_core takes them; default: drawn once, here, with a fixed seed
+    any_size   a source without a quad and targets without quads may have any size: they are resized to 1024 x 1024 as
+               `Image.resize((1024, 1024))` does (BICUBIC; the stitched 1024 x 1024 faces are returned, as in the reference), and the
+               quad paths crop with shrink=True (align.crop_faces_by_quads).  Default: both are refused."""
 
-    def __init__(self, net, reenactor, sr, restorer, parser, *, batch=1, lap_bld=False, outer_dilation=5, graph=True, noise=None):
+    def __init__(self, net, reenactor, sr, restorer, parser, *, batch=1, lap_bld=False, outer_dilation=5, graph=True, noise=None,
+                 any_size=False):
         self.is_net = hasattr(net, "get_style_vectors")
         if not self.is_net and not callable(net):
             raise TypeError("FaceSwapPipeline: net is a Net3 or a callable with face_swap_core's arguments (without the net)")
@@ -85,6 +90,7 @@ class FaceSwapPipeline(object):
             raise ValueError("FaceSwapPipeline: graph=True captures a Net3; a callable swap runs with graph=False")
         self.net, self.reenactor, self.sr, self.restorer, self.parser = net, reenactor, sr, restorer, parser
         self.batch, self.lap_bld, self.outer_dilation, self.graph = int(batch), bool(lap_bld), int(outer_dilation), bool(graph)
+        self.any_size = bool(any_size)
         self.num_cls = int(net.opts.num_seg_cls) if self.is_net else int(getattr(net, "num_seg_cls", 12))
         if noise is None and self.is_net:
             dev = next(net.parameters()).device
@@ -151,10 +157,10 @@ class FaceSwapPipeline(object):
             raise ValueError("FaceSwapPipeline.swap: a source quad needs target quads (need_crop); target quads alone are only_target_crop")
         sq = _quads(source_quad, 1, "source quads") if source_quad is not None else None
         tq = _quads(target_quads, b, "target quads") if target_quads is not None else None
-        if sq is None and tuple(src.shape) != (FACE, FACE, 3):
+        if sq is None and not self.any_size and tuple(src.shape) != (FACE, FACE, 3):
             raise ValueError(f"FaceSwapPipeline.swap: without a source quad the source is a {FACE} x {FACE} face (PIL's resize of an "
                              f"un-cropped frame is not provided), got {tuple(src.shape)}")
-        if tq is None and tuple(tgt.shape[1:]) != (FACE, FACE, 3):
+        if tq is None and not self.any_size and tuple(tgt.shape[1:]) != (FACE, FACE, 3):
             raise ValueError(f"FaceSwapPipeline.swap: without target quads the targets are {FACE} x {FACE} faces (PIL's resize of "
                              f"un-cropped frames is not provided), got {tuple(tgt.shape)}")
         if target_labels is not None:
@@ -165,8 +171,8 @@ class FaceSwapPipeline(object):
         if src.device != tgt.device:
             raise RuntimeError("FaceSwapPipeline.swap: source and targets are on different devices")
 
-        s_face = align.crop_faces_by_quads(src[None], sq, FACE) if sq is not None else src[None]              # 1
-        t_face = align.crop_faces_by_quads(tgt, tq, FACE) if tq is not None else tgt
+        s_face = align.crop_faces_by_quads(src[None], sq, FACE, shrink=self.any_size) if sq is not None else self._face(src[None])   # 1
+        t_face = align.crop_faces_by_quads(tgt, tq, FACE, shrink=self.any_size) if tq is not None else self._face(tgt)
         s_256, t_256 = K.resize_aa4(s_face), K.resize_aa4(t_face)                                             # 2
         t_lab = self.parser.parse(t_face) if target_labels is None else target_labels.contiguous()            # 3
         pred = self.reenactor.run(s_256[0], t_256)                                                            # 4
@@ -186,6 +192,13 @@ class FaceSwapPipeline(object):
             for k in ("D_labels", "swapped_labels", "hole", "swapped_face", "stitched"):
                 taps[k] = taps[k][0] if len(taps[k]) == 1 else torch.cat(taps[k])
         return align.swap_into_frames(stitched, tgt, tq) if tq is not None else stitched                      # 13
+
+    @staticmethod
+    def _face(images):
+        """face_swap.py:184,190-191 `.resize((1024, 1024))` of un-cropped images (a 1024 x 1024 image is what Pillow copies)."""
+        if tuple(images.shape[1:]) == (FACE, FACE, 3):
+            return images
+        return resize.pil_resize(images, (FACE, FACE), resize.BICUBIC)
 
     def validate(self):
         """GraphedFaceSwap.validate() of the captured swap, if there is one (one host sync)."""

@@ -1118,6 +1118,22 @@ int e4s_color_to_labels_u8(const uint8_t* rgb, uint8_t* labels, int64_t n, void*
  * [n,brush_pix], brush_pix 3 (RGB) or 4 (RGBA, alpha ignored); out may be labels. */
 int e4s_mask_brush_u8(const uint8_t* labels, const uint8_t* brush, uint8_t* out, int64_t n, int brush_pix, int comp_idx, void* stream);
 
+/* ---- Pillow's Image.resize of 8-bit RGB images (ABI v30; e4s_amd/resize.py, csrc/resize.hip; libImaging/Resample.c) ----
+ * Both passes compute, per channel, clamp((2^21 + sum_t pixel[min + t] * kk[i][t]) >> 22, 0, 255) with an arithmetic shift, from
+ * tables the host builds in float64 as Pillow does: bounds int32 [out_size,2] = {first input index, number of taps} and kk int32
+ * [out_size,ksize] (22 fractional bits), both on the device.  No access leaves the buffers whatever the tables hold.
+ * Horizontal: img uint8 [B,H,W,3] -> dst[b][r][(x - x0) * 3 + c] for the input rows ry0 + r, r = 0 .. rows - 1, and the output
+ * columns x0 .. x1 - 1 (rows dst_pitch bytes apart, images dst_bstride bytes).  A block makes tx output pixels (a power of two, 4 ..
+ * 128) of rh rows (8 or 1) from at most `span` staged input pixels per row: span is the largest number of input pixels any tx
+ * consecutive outputs read, and (span * 3 + 31) / 16 * 16 * rh must fit in 64 KiB of LDS. */
+int e4s_pil_resample_h_u8(const uint8_t* img, int B, int H, int W, const int32_t* bounds, const int32_t* kk, int ksize, int out_size,
+                          int x0, int x1, int ry0, int rows, uint8_t* dst, int64_t dst_pitch, int64_t dst_bstride, int tx, int rh,
+                          int span, void* stream);
+/* Vertical: src uint8 [B,rows,pitch] whose row r is row ry0 + r of the horizontally resampled image (pitch a multiple of 16 bytes,
+ * src 16-byte aligned, nbytes <= pitch bytes of a row in use) -> out uint8 [B,y1 - y0,nbytes], the output rows y0 .. y1 - 1. */
+int e4s_pil_resample_v_u8(const uint8_t* src, int64_t pitch, int B, int rows, int ry0, const int32_t* bounds, const int32_t* kk,
+                          int ksize, int out_size, int y0, int y1, int nbytes, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
