@@ -30,7 +30,8 @@ extern "C" {
 #endif
 
 /* ---- library info ------------------------------------------------------------------------ */
-int e4s_abi_version(void);                 /* bumped on any signature change */
+#define E4S_ABI_VERSION 30                 /* bump on any change of a signature or a struct; e4s_amd/lib.py derives its binding from this file */
+int e4s_abi_version(void);                 /* E4S_ABI_VERSION of the build */
 const char* e4s_build_arch(void);          /* "gfx950" */
 
 /* ---- 1:1 replacements of the reference's native ops ---------------------------------------- */

@@ -59,24 +59,9 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(so, name), f"{name} declared in e4s_hip.h but not exported"
     assert set(lib.SIGNATURES) | {"e4s_abi_version", "e4s_build_arch"} == declared
     so.e4s_abi_version.restype = ctypes.c_int
-    assert so.e4s_abi_version() == lib.ABI_VERSION
+    assert so.e4s_abi_version() == lib.ABI_VERSION == int(re.search(r"#define E4S_ABI_VERSION (\d+)", hdr).group(1))
     so.e4s_build_arch.restype = ctypes.c_char_p
     assert so.e4s_build_arch() == b"gfx950"
-
-
-def test_conv_params_struct_matches_header():
-    from e4s_amd import lib
-    hdr = open(os.path.join(ROOT, "include", "e4s_hip.h")).read()
-    body = hdr[hdr.index("typedef struct {"):hdr.index("} e4s_conv_params;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for stmt in body.split(";"):
-        stmt = stmt.replace("typedef struct {", "").strip()
-        if not stmt:
-            continue
-        for part in stmt.split(","):
-            names.append(re.findall(r"([A-Za-z_][A-Za-z0-9_]*)\s*$", part.strip())[0])
-    assert names == [f[0] for f in lib.ConvParams._fields_]
 
 
 def test_no_cpu_fallback():
@@ -372,43 +357,6 @@ def test_stitch_host_side_restatements():
     assert u.shape == (12, 10, 3) and bool((u == 77).all())
     one = orc.laplacian_blend_u8(c, c, np.random.RandomState(1).rand(12, 10, 3).astype(np.float32), num_levels=2)
     assert bool((one == 77).all())
-
-
-def test_rowdot_job_record_matches_the_header(tmp_path):
-    """kernels.rowdot_jobs packs e4s_rowdot_job records with struct format "qqqQQiiif": size and field offsets must be what a C
-    compiler gives the struct declared in include/e4s_hip.h."""
-    import struct
-    import subprocess
-    from e4s_amd import kernels as K
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "e4s_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n",'
-                   'sizeof(e4s_rowdot_job),offsetof(e4s_rowdot_job,in_off),offsetof(e4s_rowdot_job,in_stride),'
-                   'offsetof(e4s_rowdot_job,out_off),offsetof(e4s_rowdot_job,M),offsetof(e4s_rowdot_job,bias),'
-                   'offsetof(e4s_rowdot_job,G),offsetof(e4s_rowdot_job,O),offsetof(e4s_rowdot_job,K),'
-                   'offsetof(e4s_rowdot_job,scale));return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    assert got == [struct.calcsize(K._JOB_FMT), 0, 8, 16, 24, 32, 40, 44, 48, 52] and got[0] == 56
-
-
-def test_style_grad_job_record_matches_the_header(tmp_path):
-    """lib.StyleGradJob (ctypes) mirrors e4s_style_grad_job of include/e4s_hip.h: same size, same field offsets, and the job limit the
-    Python side enforces is the header's (the jobs travel by value in the kernel arguments: 32 of them stay under 4 KB)."""
-    import ctypes
-    import subprocess
-    from e4s_amd import lib
-    fields = [f[0] for f in lib.StyleGradJob._fields_]
-    src = tmp_path / "sg.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "e4s_hip.h"\nint main(void){printf("%zu %d", sizeof(e4s_style_grad_job), '
-                   'E4S_STYLE_GRAD_MAX_JOBS);' + "".join('printf(" %%zu", offsetof(e4s_style_grad_job, %s));' % f for f in fields) +
-                   'printf("\\n");return 0;}\n')
-    exe = tmp_path / "sg"
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    assert got[0] == ctypes.sizeof(lib.StyleGradJob) and got[1] == lib.STYLE_GRAD_MAX_JOBS
-    assert got[2:] == [getattr(lib.StyleGradJob, f).offset for f in fields]
-    assert got[0] * got[1] + 4 * (got[1] + 1) + 4 + 32 <= 4096          # jobs + block offsets + count + the other arguments of stage 2
 
 
 def test_train_iteration_cadence_follows_the_coach_loop():
