@@ -991,6 +991,57 @@ def adam_multi_dev(ps, grads, ms, vs, steps, lr, beta1, beta2, eps, weight_decay
          _ptr_array(steps, torch.int64), float(lr), ptr(lr_dev), float(beta1), float(beta2), float(eps), float(weight_decay), stream())
 
 
+def _multi_sizes(name, ps, grads, *states, lr_dev=None):
+    n = len(ps)
+    if len(grads) != n or any(len(s) != n for s in states):
+        raise RuntimeError(f"{name}: list lengths differ")
+    if lr_dev is not None and (lr_dev.dtype != torch.float64 or not lr_dev.is_cuda):
+        raise RuntimeError(f"{name}: lr_dev must be a device float64 tensor")
+    for p, g in zip(ps, grads):
+        if g.shape != p.shape:
+            raise RuntimeError(f"{name}: gradient shape differs from its parameter's")
+    for s in states:
+        for p, t in zip(ps, s):
+            if t.numel() != p.numel():
+                raise RuntimeError(f"{name}: a state tensor's size differs from its parameter's")
+    return n, (ctypes.c_int64 * n)(*[p.numel() for p in ps])
+
+
+def sgd_multi_dev(ps, grads, bufs, lr, momentum, dampening, weight_decay, lr_dev=None):
+    """torch.optim.SGD's update (nesterov=False) of lists of tensors: ceil(len / 48) launches, capturable.  bufs: the momentum buffers
+    (zeros before the first step), or None with momentum == 0."""
+    if (momentum != 0) != (bufs is not None):
+        raise RuntimeError("sgd_multi_dev: momentum buffers come with momentum != 0, and only then")
+    n, sizes = _multi_sizes("sgd_multi_dev", ps, grads, *(() if bufs is None else (bufs,)), lr_dev=lr_dev)
+    call("e4s_sgd_multi_dev_f32", n, _ptr_array(ps), _ptr_array(grads), None if bufs is None else _ptr_array(bufs), sizes, float(lr),
+         ptr(lr_dev), float(momentum), float(dampening), float(weight_decay), stream())
+
+
+def adamax_multi_dev(ps, grads, ms, us, steps, lr, beta1, beta2, eps, weight_decay, lr_dev=None):
+    """torch.optim.Adamax's update of lists of tensors: ceil(len / 48) launches, capturable.  steps: device int64[1] tensors, already
+    advanced; ms / us: exp_avg / exp_inf."""
+    n, sizes = _multi_sizes("adamax_multi_dev", ps, grads, ms, us, lr_dev=lr_dev)
+    if len(steps) != n:
+        raise RuntimeError("adamax_multi_dev: list lengths differ")
+    call("e4s_adamax_multi_dev_f32", n, _ptr_array(ps), _ptr_array(grads), _ptr_array(ms), _ptr_array(us), sizes,
+         _ptr_array(steps, torch.int64), float(lr), ptr(lr_dev), float(beta1), float(beta2), float(eps), float(weight_decay), stream())
+
+
+def scalar_log(srcs, step, log):
+    """log[step - 1, j] = srcs[j] for up to 16 one-element fp32 device tensors, `step` a device int64[1] (the step being taken, >= 1)
+    and `log` a contiguous fp32 [rows, len(srcs)]: one launch, no host sync; a step outside 1 .. rows writes nothing."""
+    if len(srcs) > 16:
+        raise RuntimeError("scalar_log: at most 16 scalars per launch")
+    if step.dtype != torch.int64 or not step.is_cuda or step.numel() != 1:
+        raise RuntimeError("scalar_log: step must be a one-element device int64 tensor")
+    if log.dtype != torch.float32 or not log.is_cuda or not log.is_contiguous() or log.dim() != 2 or log.shape[1] != len(srcs):
+        raise RuntimeError(f"scalar_log: log must be a contiguous device float32 [rows,{len(srcs)}] tensor")
+    for s in srcs:
+        if s.numel() != 1:
+            raise RuntimeError("scalar_log: the sources are one-element tensors")
+    call("e4s_scalar_log_f32", len(srcs), _ptr_array(srcs), ptr(step), fptr(log), log.shape[0], stream())
+
+
 def ranger_ws_floats(sizes, row_lens):
     """Floats of row-sum workspace ranger_multi_dev needs for tensors of `sizes` elements whose centralised rows are `row_lens` long
     (0: the tensor's gradient is not centralised)."""

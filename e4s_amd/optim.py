@@ -321,6 +321,167 @@ class Ranger(FusedAdam):
         return loss
 
 
+class FusedSGD(FusedAdam):
+    """torch.optim.SGD (nesterov=False, maximize=False) as a fused, always-capturable step: `setup_W_optimizer`'s 'sgd' and 'sgdm'
+    (scripts/optimization.py:134-139).  All parameters of a group go out as ceil(n / 48) launches of e4s_sgd_multi_dev_f32; the
+    learning rate is read from a device float64 (a changed `group["lr"]` reaches a replayed GraphedStep), momentum / dampening /
+    weight_decay travel by value.  The param_groups carry torch's keys and the state torch's `momentum_buffer` (absent with
+    momentum == 0), so a state_dict() loads into torch.optim.SGD and back.  The buffer is created as zeros: momentum * 0 + g is g
+    exactly, torch's first-step clone; with dampening != 0 torch's first buffer is g where this one is (1 - dampening) g.  There is no
+    step count, hence no flat step tensor.  fp32 parameters with dense fp32 gradients only; there is no CPU path."""
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0):
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=False, maximize=False,
+                        foreach=None, differentiable=False, fused=None)
+        torch.optim.Optimizer.__init__(self, params, defaults)
+        self.capturable = True
+        self._dev = {}                    # FusedAdam's per-group record ("flat" stays None)
+        self._stepped = {}                # id -> parameter, every one step() has written
+
+    def hyper_by_value(self):
+        """What a captured step bakes into its kernel arguments besides addresses: (momentum, dampening, weight_decay) of every group."""
+        return tuple((float(g["momentum"]), float(g["dampening"]), float(g["weight_decay"])) for g in self.param_groups)
+
+    def captured_state_ptrs(self):
+        """Addresses a captured step has baked into its kernel arguments: the momentum buffers."""
+        out = []
+        for group in self.param_groups:
+            for p in group["params"]:
+                buf = self.state.get(p, {}).get("momentum_buffer")
+                if buf is not None:
+                    out.append(buf.data_ptr())
+        return tuple(out)
+
+    def written_tensors(self):
+        return list(self._stepped.values())
+
+    def _check(self, p):
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise RuntimeError("FusedSGD handles contiguous fp32 parameters")
+        if p.grad.is_sparse or p.grad.device != p.device or p.grad.dtype != torch.float32:
+            raise RuntimeError("FusedSGD needs a dense fp32 gradient on the parameter's device")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        capturing = torch.cuda.is_current_stream_capturing()
+        if not capturing:
+            self.sync_hyper()
+        for gi, group in enumerate(self.param_groups):
+            if group["nesterov"] or group["maximize"]:
+                raise NotImplementedError("FusedSGD: nesterov / maximize are not implemented")
+            live = [p for p in group["params"] if p.grad is not None]
+            if not live:
+                continue
+            momentum = float(group["momentum"])
+            for p in live:
+                self._check(p)
+                if momentum != 0 and self.state[p].get("momentum_buffer") is None:
+                    if capturing:
+                        raise RuntimeError("FusedSGD: a parameter got its first gradient inside a graph capture; take one eager step first")
+                    self.state[p]["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                self._stepped[id(p)] = p
+            d = self._group_dev(gi, group, live[0].device)
+            d["hyper"] = self.hyper_by_value()[gi]
+            grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in live]
+            K.sgd_multi_dev(live, grads, [self.state[p]["momentum_buffer"] for p in live] if momentum != 0 else None, group["lr"],
+                            momentum, group["dampening"], group["weight_decay"], lr_dev=d["lr"])
+            torch.autograd.graph.increment_version(live)     # raw-pointer writes: keep (data_ptr, _version) pack keys honest
+        return loss
+
+
+class FusedAdamax(FusedAdam):
+    """torch.optim.Adamax (maximize=False) as a fused, always-capturable step: `setup_W_optimizer`'s 'adamax'.  The arithmetic is
+    `_single_tensor_adamax`'s non-capturable path with 1 - beta1^t evaluated in the kernel, in double, from the device step count
+    (e4s_adamax_multi_dev_f32).  The step counts of a group live in one flat device int64 tensor (`state[p]["step"]` is a view of it,
+    as FusedAdam's), the learning rate in a device float64; betas / eps / weight_decay travel by value.  param_groups carry torch's
+    keys and the state torch's (`step`, `exp_avg`, `exp_inf`): a state_dict() loads into torch.optim.Adamax and back."""
+
+    def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid betas: {betas}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, foreach=None, maximize=False, differentiable=False,
+                        capturable=False)            # (`capturable` is torch.optim.Adamax's own flag, for the round trip; this class always is)
+        torch.optim.Optimizer.__init__(self, params, defaults)
+        self.capturable = True
+        self._dev = {}
+
+    def captured_state_ptrs(self):
+        """Addresses a captured step has baked into its kernel arguments: per group the flat step tensor, per parameter exp_avg / exp_inf."""
+        out = []
+        for gi, group in enumerate(self.param_groups):
+            d = self._dev.get(gi)
+            out.append(d["flat"].data_ptr() if d is not None and d.get("flat") is not None else 0)
+            for p in group["params"]:
+                st = self.state.get(p)
+                if st and "exp_avg" in st:
+                    out.extend((st["exp_avg"].data_ptr(), st["exp_inf"].data_ptr()))
+        return tuple(out)
+
+    def _check(self, p):
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise RuntimeError("FusedAdamax handles contiguous fp32 parameters")
+        if p.grad.is_sparse or p.grad.device != p.device or p.grad.dtype != torch.float32:
+            raise RuntimeError("FusedAdamax needs a dense fp32 gradient on the parameter's device")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        capturing = torch.cuda.is_current_stream_capturing()
+        if not capturing:
+            self.sync_hyper()
+        for gi, group in enumerate(self.param_groups):
+            if group["maximize"]:
+                raise NotImplementedError("FusedAdamax: maximize is not implemented")
+            b1, b2 = group["betas"]
+            live = [p for p in group["params"] if p.grad is not None]
+            if not live:
+                continue
+            for p in live:
+                self._check(p)
+                st = self.state[p]
+                if "exp_avg" not in st:
+                    if capturing:
+                        raise RuntimeError("FusedAdamax: a parameter got its first gradient inside a graph capture; take one eager step first")
+                    st["step"] = 0
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    st["exp_inf"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            dev = live[0].device
+            d = self._group_dev(gi, group, dev)
+            d["hyper"] = self.hyper_by_value()[gi]
+            with_state = [p for p in group["params"] if p in self.state and "exp_avg" in self.state[p]]
+            flat = self._flat_steps(d, with_state, dev)
+            if len(live) == len(with_state):
+                K.advance_steps(flat)                            # one launch for the whole group
+            else:                                                # some parameters have no gradient this step: theirs do not advance
+                for p in live:
+                    K.advance_steps(self.state[p]["step"])
+            grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in live]
+            K.adamax_multi_dev(live, grads, [self.state[p]["exp_avg"] for p in live], [self.state[p]["exp_inf"] for p in live],
+                               [self.state[p]["step"] for p in live], group["lr"], b1, b2, group["eps"], group["weight_decay"],
+                               lr_dev=d["lr"])
+            torch.autograd.graph.increment_version(live)
+        return loss
+
+
 class GraphedStep:
     """One optimisation step captured in a HIP graph.  `body()` runs forward + backward + `opt.step()` for a capturable
     optimiser and returns the loss tensor; it must be free of host synchronisation and read its inputs from tensors whose

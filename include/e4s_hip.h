@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library info ------------------------------------------------------------------------ */
-#define E4S_ABI_VERSION 30                 /* bump on any change of a signature or a struct; e4s_amd/lib.py derives its binding from this file */
+#define E4S_ABI_VERSION 31                 /* bump on any change of a signature or a struct; e4s_amd/lib.py derives its binding from this file */
 int e4s_abi_version(void);                 /* E4S_ABI_VERSION of the build */
 const char* e4s_build_arch(void);          /* "gfx950" */
 
@@ -468,6 +468,27 @@ int e4s_adam_multi_dev_f32(int count, float* const* p, const float* const* grad,
                            const int64_t* const* step, double lr, const double* lr_dev, double beta1, double beta2, double eps,
                            double weight_decay, void* stream);
 int e4s_ema_multi_f32(int count, float* const* dst, const float* const* src, const int64_t* n, double decay, void* stream);
+/* The other optimisers of scripts/optimization.py:134-139 in the calling convention of e4s_adam_multi_dev_f32 (ABI v31; csrc/invert.hip,
+ * e4s_amd/optim.py:FusedSGD / FusedAdamax): HOST arrays of device pointers handed to the kernels by value, 48 tensors per launch; lr_dev:
+ * optional DEVICE double that overrides `lr`; every other hyper-parameter by value; no allocation, copy or synchronisation: capturable.
+ * 16-byte accesses where p / grad / state of a tensor are all 16-byte aligned, 4-byte accesses otherwise and on a tensor's tail.
+ * e4s_sgd_multi_dev_f32: torch.optim.SGD (nesterov=False), one rounding per operation:
+ *   g' = g + wd p  (wd != 0);  buf = buf momentum + (1 - dampening) g';  p += (-lr) buf;      momentum == 0: p += (-lr) g', buf may be NULL
+ *   buf starts as ZEROS (momentum * 0 + g' is g' exactly: torch's first-step clone, without a step count; with dampening != 0 torch's
+ *   first buffer is g' where this one is (1 - dampening) g').
+ * e4s_adamax_multi_dev_f32: torch.optim.Adamax as _single_tensor_adamax computes it on its non-capturable path:
+ *   g' = g + wd p  (wd != 0);  m = lerp(m, g', 1 - b1);  u = max(b2 u, |g'| + eps);  p += -(lr / (1 - b1^t)) (m / u)
+ *   t = *step[i]: DEVICE int64, already advanced (e4s_advance_i64), >= 1 (a count < 1 leaves its tensor untouched); b1^t is evaluated in
+ *   double in the kernel.  u >= eps: a zero gradient at t = 1 gives m = 0 and an update of 0. */
+int e4s_sgd_multi_dev_f32(int count, float* const* p, const float* const* grad, float* const* buf, const int64_t* n, double lr,
+                          const double* lr_dev, double momentum, double dampening, double weight_decay, void* stream);
+int e4s_adamax_multi_dev_f32(int count, float* const* p, const float* const* grad, float* const* m, float* const* u, const int64_t* n,
+                             const int64_t* const* step, double lr, const double* lr_dev, double beta1, double beta2, double eps,
+                             double weight_decay, void* stream);
+/* The loss_dict of scripts/optimization.py:88-122 kept on the device: log[(t - 1) * count + j] = *src[j] for j < count <= 16 and
+ * t = *step_dev (DEVICE int64, the step being taken); src: HOST array of device pointers to fp32 scalars, handed to the kernel by value.
+ * One launch, capturable; t < 1 or t - 1 >= rows writes nothing. */
+int e4s_scalar_log_f32(int count, const float* const* src, const int64_t* step_dev, float* log, int64_t rows, void* stream);
 /* Ranger = RAdam + Lookahead + gradient centralisation (src/training/ranger.py:78-164) as a multi-tensor capturable step (ABI v21;
  * csrc/ranger.hip, e4s_amd/optim.py:Ranger).  Arrays as in e4s_adam_multi_dev_f32 (HOST arrays of device pointers, handed to the kernels
  * by value, 40 tensors per launch) plus slow[i] (Lookahead's slow weights) and row_len[i]: the length of one row (index 0) of tensor i if
