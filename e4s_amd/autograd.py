@@ -18,6 +18,7 @@ from torch.autograd.function import once_differentiable
 
 from .tape import Tape
 from . import kernels as K
+from . import packs
 
 
 def styled_conv_backward(rec, dy, num_regions, extras=None, defer=None):
@@ -42,10 +43,10 @@ def styled_conv_backward(rec, dy, num_regions, extras=None, defer=None):
         # one style per sample: dx = s * conv(gz * d, flipped W^T) is the FORWARD split-bf16 contraction on re-packed weights (the
         # exact-fp32 dx + ds kernel ran the 64->64@512^2 / 32->32@1024^2 dgrads of the optimisation step at 0.69 / 0.71 ms, the forward
         # kernels take ~0.1); ds = sum_p x * (the same contraction) leaves the pass that applies s
-        if "wt_fwd" not in pk:
+        def wt_fwd(pk):
             wp = K.pack_taps_bwd(pk["w"], out=conv._buf("wt_fwd", (1, 9, cin, cout), x.device))           # [1,9,Cin,Cout], taps flipped (one launch)
-            pk["wt_fwd"] = (wp, K.split_bf16x2(wp, out=conv._buf("wt_fwd_split", (1, 9, cin, cout), x.device)))
-        wp, wps = pk["wt_fwd"]
+            return wp, K.split_bf16x2(wp, out=conv._buf("wt_fwd_split", (1, 9, cin, cout), x.device))
+        wp, wps = packs.derived(conv, "w", "wt_fwd", wt_fwd)                     # (conv.packed() above made the slot current)
         if cout == 32 and cin % 32 == 0:
             u = K.conv_c32(gz.contiguous(), wps, cin, in_scale=d)
         else:
@@ -57,12 +58,12 @@ def styled_conv_backward(rec, dy, num_regions, extras=None, defer=None):
         # (e4s_pixel_unshuffle2_f32) the dgrad is ONE 'same' 3x3 convolution with 4*Cout input channels on the forward split-bf16 kernel:
         # dx = s * conv(unshuffle(gz) * d, flipped Weff^T), ds from the pass that applies s.  (The exact-fp32 dx + ds kernel ran these two
         # dgrads at ~0.5 / 1.0 ms per image: 36 multiply-adds per input pixel and channel pair on v_mfma_f32_32x32x2_f32.)
-        if "wt_up_fwd" not in pk:
+        def wt_up_fwd(pk):
             wp = pk["w"].flip(1).permute(1, 3, 0, 2).reshape(1, 9, cin, 4 * cout).contiguous()     # [1,9,Cin,(phase,Cout)]
             keep = conv._buf("wt_up_fwd", tuple(wp.shape), wp.device)
             keep.copy_(wp)
-            pk["wt_up_fwd"] = (keep, K.split_bf16x2(keep, out=conv._buf("wt_up_fwd_split", tuple(wp.shape), wp.device)))
-        wp, wps = pk["wt_up_fwd"]
+            return keep, K.split_bf16x2(keep, out=conv._buf("wt_up_fwd_split", tuple(wp.shape), wp.device))
+        wp, wps = packs.derived(conv, "w", "wt_up_fwd", wt_up_fwd)
         u = K.conv_mfma(K.pixel_unshuffle2(gz), wp, cin, w_split=wps, in_scale=d.repeat(1, 4).contiguous())
         dx, ds = K.scale_dot(u, x, s)
     elif labels is not None and x.is_contiguous() and K.scatter_dgrad_wanted(b, h, w, cout, cin):

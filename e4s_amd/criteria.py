@@ -38,7 +38,7 @@ import functools
 
 from . import kernels as K
 from .encoders import SEModule, _conv3x3, _conv_strided, get_block
-from .packs import param_key
+from . import packs
 
 
 def _plain_split(fn):
@@ -86,25 +86,20 @@ class _Taps:
 
 def _transposed(conv):
     """The dgrad operand of a k x k conv: taps flipped, in/out channels swapped (cached; the networks are frozen)."""
-    key = param_key(conv.weight)
-    if getattr(conv, "_e4s_t", None) is None or conv._e4s_t[0] != key:
-        with torch.no_grad():
-            conv._e4s_t = (key, _Taps(conv.weight.detach().float().flip(2, 3).transpose(0, 1).contiguous()))
-    return conv._e4s_t[1]
+    return packs.cached(conv, "transposed", (conv.weight,),
+                        lambda: _Taps(conv.weight.detach().float().flip(2, 3).transpose(0, 1).contiguous()))
 
 
 def _bn_stats(bn, batch):
     """BatchNorm in eval mode as the kernels' {mean, rstd} operand: gamma*(x-m)/sqrt(v+eps)+beta = (x - mu') * rho' with
     rho' = gamma/sqrt(v+eps), mu' = m - beta/rho'.  [B,C,2], cached per (parameters, batch)."""
-    key = (param_key(bn.weight), param_key(bn.bias), bn.running_mean._version, bn.running_var._version, batch)
-    if getattr(bn, "_e4s_stats", None) is None or bn._e4s_stats[0] != key:
-        with torch.no_grad():
-            rho = bn.weight.float() / torch.sqrt(bn.running_var.float() + bn.eps)
-            if bool((rho.abs() < 1e-30).any()):
-                raise RuntimeError("BatchNorm with a zero scale cannot be folded into the conv's operand staging")
-            mu = bn.running_mean.float() - bn.bias.float() / rho
-            bn._e4s_stats = (key, torch.stack([mu, rho], 1)[None].expand(batch, -1, -1).contiguous())
-    return bn._e4s_stats[1]
+    def build():
+        rho = bn.weight.float() / torch.sqrt(bn.running_var.float() + bn.eps)
+        if bool((rho.abs() < 1e-30).any()):
+            raise RuntimeError("BatchNorm with a zero scale cannot be folded into the conv's operand staging")
+        mu = bn.running_mean.float() - bn.bias.float() / rho
+        return torch.stack([mu, rho], 1)[None].expand(batch, -1, -1).contiguous()
+    return packs.cached(bn, "stats", (bn.weight, bn.bias, bn.running_mean, bn.running_var), build, (batch,))
 
 
 def _se_weights(se):
@@ -212,22 +207,20 @@ class Backbone(Module):
         """BatchNorm2d(512) -> Flatten (NCHW order) -> Linear -> BatchNorm1d as ONE affine map on the NHWC-flattened feature:
         (W'' [1,512,25088], b'' [1,512]), cached."""
         bn2, _, _, lin, bn1 = self.output_layer
-        key = (param_key(lin.weight), param_key(lin.bias), param_key(bn2.weight), param_key(bn2.bias), bn2.running_mean._version,
-               bn2.running_var._version, bn1.running_mean._version, bn1.running_var._version,
-               param_key(bn1.weight) if bn1.affine else None)
-        if getattr(self, "_e4s_head", None) is None or self._e4s_head[0] != key:
-            with torch.no_grad():
-                s2 = bn2.weight.float() / torch.sqrt(bn2.running_var.float() + bn2.eps)           # [512] per channel
-                t2 = bn2.bias.float() - bn2.running_mean.float() * s2
-                w = lin.weight.float().view(512, 512, 49)                                          # [o, c, p]
-                bias = lin.bias.float() + (w * t2[None, :, None]).sum((1, 2))
-                w = (w * s2[None, :, None]).permute(0, 2, 1).reshape(512, 49 * 512)               # [o, p*512 + c]
-                s1 = torch.rsqrt(bn1.running_var.float() + bn1.eps)
-                t1 = -bn1.running_mean.float() * s1
-                if bn1.affine:
-                    s1, t1 = s1 * bn1.weight.float(), t1 * bn1.weight.float() + bn1.bias.float()
-                self._e4s_head = (key, (w * s1[:, None]).contiguous()[None], (bias * s1 + t1).contiguous()[None])
-        return self._e4s_head[1], self._e4s_head[2]
+
+        def build():
+            s2 = bn2.weight.float() / torch.sqrt(bn2.running_var.float() + bn2.eps)           # [512] per channel
+            t2 = bn2.bias.float() - bn2.running_mean.float() * s2
+            w = lin.weight.float().view(512, 512, 49)                                          # [o, c, p]
+            bias = lin.bias.float() + (w * t2[None, :, None]).sum((1, 2))
+            w = (w * s2[None, :, None]).permute(0, 2, 1).reshape(512, 49 * 512)               # [o, p*512 + c]
+            s1 = torch.rsqrt(bn1.running_var.float() + bn1.eps)
+            t1 = -bn1.running_mean.float() * s1
+            if bn1.affine:
+                s1, t1 = s1 * bn1.weight.float(), t1 * bn1.weight.float() + bn1.bias.float()
+            return (w * s1[:, None]).contiguous()[None], (bias * s1 + t1).contiguous()[None]
+        tensors = (lin.weight, lin.bias, bn2.weight, bn2.bias, bn2.running_mean, bn2.running_var, bn1.running_mean, bn1.running_var)
+        return packs.cached(self, "head", tensors + ((bn1.weight, bn1.bias) if bn1.affine else ()), build)
 
     def features_nhwc(self, x112, multi_scale, tape=None):
         """x112 NHWC [B,112,112,3] -> the compared features, NOT yet l2-normalised (the cosine kernel normalises): the four
@@ -275,16 +268,13 @@ class Backbone(Module):
 
 
 def _smallcin_pack(conv):
-    key = param_key(conv.weight)
-    if getattr(conv, "_e4s_small", None) is None or conv._e4s_small[0] != key:
-        conv._e4s_small = (key, K.pack_smallcin(conv.weight), {})      # the dict: derived images of this pack (conv_smallcin_bwd's GEMM form)
-    return conv._e4s_small[1]
+    return packs.cached(conv, "smallcin", (conv.weight,), lambda: K.pack_smallcin(conv.weight))
 
 
 def _smallcin_cache(conv):
     """The per-pack cache handed to K.conv_smallcin_bwd (lives and dies with the pack of THIS conv)."""
     _smallcin_pack(conv)
-    return conv._e4s_small[2]
+    return packs.derived(conv, "smallcin", "bwd", lambda _: {})       # (conv_smallcin_bwd keeps the GEMM form of the pack in it)
 
 
 class _IDLossFn(torch.autograd.Function):
@@ -478,11 +468,7 @@ class AlexNet(Module):
 
 def _pack(conv):
     """[1, k*k, Cout, Cin] taps of a conv (cached on the module)."""
-    key = param_key(conv.weight)
-    if getattr(conv, "_e4s_pack", None) is None or conv._e4s_pack[0] != key:
-        with torch.no_grad():
-            conv._e4s_pack = (key, K.pack_taps(conv.weight.detach().float().contiguous()))
-    return conv._e4s_pack[1]
+    return packs.cached(conv, "taps", (conv.weight,), lambda: K.pack_taps(conv.weight.detach().float().contiguous()))
 
 
 class _LPIPSFn(torch.autograd.Function):
@@ -597,19 +583,17 @@ def _folded(seq, cin_pad, cout_pad):
     (cout_pad, cin_pad) channels (16-channel maps ride the 32-channel K step; the padded channels stay exactly 0 through
     bias-free ReLU, so cosines over the padded maps equal those over the real ones).  Returns a `_Taps` holder with .bias."""
     conv, bn = seq[0], seq[1]
-    key = (param_key(conv.weight), param_key(conv.bias), param_key(bn.weight), param_key(bn.bias), bn.running_mean._version,
-           bn.running_var._version, cin_pad, cout_pad)
-    if getattr(seq, "_e4s_fold", None) is None or seq._e4s_fold[0] != key:
-        with torch.no_grad():
-            s = bn.weight.float() / torch.sqrt(bn.running_var.float() + bn.eps)
-            w = conv.weight.float() * s[:, None, None, None]
-            b = (conv.bias.float() - bn.running_mean.float()) * s + bn.bias.float()
-            cout, cin = w.shape[:2]
-            w = nn.functional.pad(w, (0, 0, 0, 0, 0, cin_pad - cin, 0, cout_pad - cout)).contiguous()
-            t = _Taps(w)
-            t.bias = nn.functional.pad(b, (0, cout_pad - cout)).contiguous()
-            seq._e4s_fold = (key, t)
-    return seq._e4s_fold[1]
+
+    def build():
+        s = bn.weight.float() / torch.sqrt(bn.running_var.float() + bn.eps)
+        w = conv.weight.float() * s[:, None, None, None]
+        b = (conv.bias.float() - bn.running_mean.float()) * s + bn.bias.float()
+        cout, cin = w.shape[:2]
+        w = nn.functional.pad(w, (0, 0, 0, 0, 0, cin_pad - cin, 0, cout_pad - cout)).contiguous()
+        t = _Taps(w)
+        t.bias = nn.functional.pad(b, (0, cout_pad - cout)).contiguous()
+        return t
+    return packs.cached(seq, "fold", (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var), build, (cin_pad, cout_pad))
 
 
 class unet(Module):

@@ -22,53 +22,32 @@ from torch.autograd import Function
 
 from . import kernels as K
 from .lib import call, fptr, stream
-from .packs import param_key
+from . import packs
 
 
 # ---- conv family ------------------------------------------------------------------------------------------------
-class _PackCache:
-    """Tap-packed / transposed / split-bf16 images of ONE ConvLayer weight, valid for one (storage, version) of the parameter
-    (packs.param_key).  While D is frozen (the generator step, 14 of 15 iterations) nothing is re-packed; while it trains, the
-    three or four uses inside one step (D(fake), D(real), their backward) share one pack."""
-    __slots__ = ("key", "packs")
-
-    def __init__(self):
-        self.key, self.packs = None, {}
-
-    def get(self, key, name, make):
-        if self.key != key:
-            self.key, self.packs = key, {}
-        if name not in self.packs:
-            self.packs[name] = make()
-        return self.packs[name]
-
-
-def invalidate_packs(disc):
-    """Forget D's cached weight packs (a captured graph that must re-pack from the weights of the moment: train.graphed_g_step)."""
-    for m in disc.modules():
-        pc = getattr(m, "_e4s_dpacks", None)
-        if pc is not None:
-            pc.key, pc.packs = None, {}
-
-
+# cache: the (owner, slot, key) of packs.cached when `w` IS a ConvLayer's (scaled, padded) weight (_conv_layer made the slot current) -- the
+# tap-packed / transposed / split-bf16 images then hang on it (packs.derived) and are shared between calls: while D is frozen (the generator
+# step, 14 of 15 iterations) nothing is re-packed; while it trains, the three or four uses inside one step (D(fake), D(real), their
+# backward) share one pack.  None for the second-order nodes, whose `w` operand is a gradient: packed per call.
 def _pack(w, cache=None):
-    make = lambda: K.pack_taps(w.detach().float().contiguous())
-    return cache[0].get(cache[1], "fwd", make) if cache is not None else make()
+    make = lambda _: K.pack_taps(w.detach().float().contiguous())
+    return packs.derived(cache[0], cache[1], "fwd", make, cache[2]) if cache is not None else make(None)
 
 
 def _pack_t(w, cache=None):
     if w.shape[2] == 3:          # one launch from the forward pack (was flip + transpose copy + pack)
-        make = lambda: K.pack_taps_bwd(_pack(w, cache))
+        make = lambda _: K.pack_taps_bwd(_pack(w, cache))
     else:
-        make = lambda: K.pack_taps(w.detach().float().flip(2, 3).transpose(0, 1).contiguous())
-    return cache[0].get(cache[1], "bwd", make) if cache is not None else make()
+        make = lambda _: K.pack_taps(w.detach().float().flip(2, 3).transpose(0, 1).contiguous())
+    return packs.derived(cache[0], cache[1], "bwd", make, cache[2]) if cache is not None else make(None)
 
 
 def _conv_s1(x, wp, cout, cache=None, name=None):
     b, h, w, cx = x.shape
     if K.want_bf16x3(b, h, w, cx, cout):
-        make = lambda: K.split_bf16x2(wp)
-        ws = cache[0].get(cache[1], name + "_split", make) if cache is not None else make()
+        make = lambda _: K.split_bf16x2(wp)
+        ws = packs.derived(cache[0], cache[1], name + "_split", make, cache[2]) if cache is not None else make(None)
         return K.conv_mfma(x, wp, cout, w_split=ws)
     return K.conv_mfma(x, wp, cout)
 
@@ -113,8 +92,7 @@ def _conv_wgrad(gy, x, kind, w_shape):
 
 
 class Conv(Function):
-    """cache: (_PackCache, key) when `w` IS a ConvLayer's (scaled, padded) weight -- the packs are then shared between calls;
-    None for the second-order nodes, whose `w` operand is a gradient."""
+    """cache: see above (None for the second-order nodes)."""
 
     @staticmethod
     def forward(ctx, x, w, kind, cache=None):
@@ -350,10 +328,8 @@ def _conv_layer(layer, x):
     kind = "s1" if conv.stride == 1 else ("s2k3" if k == 3 else "s2k1")
     if (kind == "s1" and (k != 3 or conv.padding != 1)) or (kind != "s1" and conv.padding != 0):
         raise NotImplementedError("ConvLayer geometry outside model.py:683-703")
-    pc = getattr(conv, "_e4s_dpacks", None)
-    if pc is None:
-        pc = conv._e4s_dpacks = _PackCache()
-    y = Conv.apply(x, w, kind, (pc, param_key(conv.weight) + (cx,)))
+    packs.cached(conv, "disc", (conv.weight,), lambda: None, (cx,))                  # every image of `w` is derived, on first use
+    y = Conv.apply(x, w, kind, (conv, "disc", packs.param_key(conv.weight) + (cx,)))   # the key: a backward after a re-pack is refused
     if isinstance(tail, FusedLeakyReLU):
         return BiasAct.apply(y, tail.bias, tail.negative_slope, tail.scale)
     if isinstance(tail, ScaledLeakyReLU):

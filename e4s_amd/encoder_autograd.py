@@ -18,6 +18,7 @@ from torch.autograd.function import once_differentiable
 
 from .tape import Tape, pack as pack_record
 from . import kernels as K
+from . import packs
 from .ddp import notify_grad
 from .encoders import _pack3x3, _conv3x3, _conv_strided
 
@@ -33,11 +34,14 @@ def _wgrad(gz, xin, stride, ntaps):
 
 def _wt(conv):
     """backward-packed (flipped, transposed) taps of a 3x3 conv, cached with the forward pack."""
-    w = _pack3x3(conv)
-    key = conv._e4s_pack[0]
-    if getattr(conv, "_e4s_wt", None) is None or conv._e4s_wt[0] != key:
-        conv._e4s_wt = (key, K.pack_taps_bwd(w))
-    return conv._e4s_wt[1]
+    _pack3x3(conv)
+    return packs.derived(conv, "taps", "bwd", K.pack_taps_bwd)
+
+
+def _wt_fwd(w):
+    """(wp, its split-bf16 image): [1,9,Cin,Cout], taps flipped: one launch from the forward pack (was flip + transpose copy + pack)"""
+    wp = K.pack_taps_bwd(w)
+    return wp, K.split_bf16x2(wp)
 
 
 def _dgrad3x3(gz, conv, x):
@@ -49,16 +53,11 @@ def _dgrad3x3(gz, conv, x):
     b, h, w, cy = gz.shape
     cx = conv.weight.shape[1]
     if K.want_bf16x3(b, h, w, cy, cx):
-        key = _pack3x3(conv) is not None and conv._e4s_pack[0]
-        cached = getattr(conv, "_e4s_wt_fwd", None)
-        if cached is None or cached[0] != key:
-            wp = K.pack_taps_bwd(_pack3x3(conv))      # [1,9,Cin,Cout], taps flipped: one launch from the forward pack (was flip + transpose copy + pack)
-            conv._e4s_wt_fwd = cached = (key, wp, K.split_bf16x2(wp), {})
+        _pack3x3(conv)
+        wp, wps = packs.derived(conv, "taps", "bwd_fwd", _wt_fwd)
         if K.wino_eligible(b, h, w, cy, cx):       # Winograd F(2,3) form of the same convolution (csrc/conv_wino.hip): 1.5x fewer MFMAs
-            if "u" not in cached[3]:
-                cached[3]["u"] = K.wino_weights(cached[1])
-            return K.conv_wino(gz.contiguous(), cached[3]["u"], cx)
-        return K.conv_mfma(gz.contiguous(), cached[1], cx, w_split=cached[2])
+            return K.conv_wino(gz.contiguous(), packs.derived(conv, "taps", "bwd_wino", lambda _: K.wino_weights(wp)), cx)
+        return K.conv_mfma(gz.contiguous(), wp, cx, w_split=wps)
     dx, _ = K.conv_bwd(gz, _wt(conv), x, None, None, None, 1, 1, want_ds=False)       # x: shape only (no ds asked for)
     return dx
 

@@ -16,7 +16,7 @@ from torch import nn
 from torch.nn import Conv2d, InstanceNorm2d, MaxPool2d, Module, PReLU, ReLU, Sequential, Sigmoid, AdaptiveAvgPool2d
 
 from . import kernels as K
-from .packs import param_key
+from . import packs
 
 
 class Bottleneck(namedtuple("Block", ["in_channel", "depth", "stride"])):
@@ -30,11 +30,7 @@ def get_block(in_channel, depth, num_units, stride=2):
 def _pack3x3(conv):
     """[Cout,Cin,3,3] -> [1,9,Cout,Cin] (cached on the module, invalidated by in-place updates)."""
     w = conv.weight
-    key = param_key(w)
-    if getattr(conv, "_e4s_pack", None) is None or conv._e4s_pack[0] != key:
-        with torch.no_grad():
-            conv._e4s_pack = (key, K.pack_taps(w.detach().float().contiguous()))
-    return conv._e4s_pack[1]
+    return packs.cached(conv, "taps", (w,), lambda: K.pack_taps(w.detach().float().contiguous()))
 
 
 def _conv3x3(x, conv, cout, in_stats=None, want_stats=False, **kw):
@@ -46,13 +42,9 @@ def _conv3x3(x, conv, cout, in_stats=None, want_stats=False, **kw):
     if K.wino_eligible(x.shape[0], x.shape[1], x.shape[2], x.shape[3], cout, in_stats=in_stats is not None) and set(kw) <= {"bias", "slope", "act", "alpha", "gain", "se"} \
             and not (want_stats and kw.get("act", 0) != 0):
         # Winograd F(2,3) along the rows: 1.5x fewer MFMAs than the direct split-bf16 kernel (csrc/conv_wino.hip)
-        if getattr(conv, "_e4s_wino", None) is None or conv._e4s_wino[0] != conv._e4s_pack[0]:
-            conv._e4s_wino = (conv._e4s_pack[0], K.wino_weights(w))
-        return K.conv_wino(x, conv._e4s_wino[1], cout, in_stats=in_stats, want_stats=want_stats, **kw)
+        return K.conv_wino(x, packs.derived(conv, "taps", "wino", K.wino_weights), cout, in_stats=in_stats, want_stats=want_stats, **kw)
     if K.want_bf16x3(x.shape[0], x.shape[1], x.shape[2], x.shape[3], cout):
-        if getattr(conv, "_e4s_split", None) is None or conv._e4s_split[0] != conv._e4s_pack[0]:
-            conv._e4s_split = (conv._e4s_pack[0], K.split_bf16x2(w))
-        return K.conv_mfma(x, w, cout, w_split=conv._e4s_split[1], in_stats=in_stats, want_stats=want_stats, **kw)
+        return K.conv_mfma(x, w, cout, w_split=packs.derived(conv, "taps", "split", K.split_bf16x2), in_stats=in_stats, want_stats=want_stats, **kw)
     if in_stats is not None:
         x = K.instnorm_apply(x, in_stats)
     return K.conv_mfma(x, w, cout, want_stats=want_stats, **kw)
@@ -74,14 +66,10 @@ def _conv_strided(x, conv, cout, stride, ntaps, want_stats=False, se=None, **kw)
     w = _pack3x3(conv)
     b, h, wd, cin = x.shape
     if strided_bf16x3(b, h, wd, cin, cout, stride, ntaps):
-        if getattr(conv, "_e4s_split", None) is None or conv._e4s_split[0] != conv._e4s_pack[0]:
-            conv._e4s_split = (conv._e4s_pack[0], K.split_bf16x2(w))
-        frag = None
-        if cout % 128 == 0:               # whole 128-column tiles: the one-wave-per-SIMD gather kernel, weights from the fragment-major image
-            if getattr(conv, "_e4s_frag", None) is None or conv._e4s_frag[0] != conv._e4s_pack[0]:
-                conv._e4s_frag = (conv._e4s_pack[0], K.gather_frag_bf16x2(w))
-            frag = conv._e4s_frag[1]
-        return K.conv_mfma(x, w, cout, istride=stride, ntaps=ntaps, w_split=conv._e4s_split[1], w_frag=frag, want_stats=want_stats, se=se, **kw)
+        split = packs.derived(conv, "taps", "split", K.split_bf16x2)
+        # whole 128-column tiles: the one-wave-per-SIMD gather kernel, weights from the fragment-major image
+        frag = packs.derived(conv, "taps", "frag", K.gather_frag_bf16x2) if cout % 128 == 0 else None
+        return K.conv_mfma(x, w, cout, istride=stride, ntaps=ntaps, w_split=split, w_frag=frag, want_stats=want_stats, se=se, **kw)
     return K.conv_mfma(x, w, cout, istride=stride, ntaps=ntaps, want_stats=want_stats, se=se, **kw)
 
 

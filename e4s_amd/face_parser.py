@@ -5,8 +5,8 @@ CelebAMask-HQ classes to the 12 E4S classes (src/datasets/dataset.py:60-108) and
 is `FaceParser.parse(images, seg12=True, onehot=True)` on a batch, every step on the device, no host synchronisation.
 
 Module tree / state_dict identical to the reference (model.py:20-289, resnet.py:14-80), so a real `79999_iter.pth`
-loads with strict=True.  BatchNorm is folded into the conv weights once per weight version (cached on the module as
-`_e4s_fold`).  Execution on NHWC tensors:
+loads with strict=True.  BatchNorm is folded into the conv weights once per weight version (packs.cached, on
+the module).  Execution on NHWC tensors:
 
     reference                                         here
     ------------------------------------------------  --------------------------------------------------------------------
@@ -31,7 +31,7 @@ from torch import nn
 
 from . import kernels as K
 from .encoders import _conv3x3, _conv_strided, _pack3x3
-from .packs import param_key
+from . import packs
 
 N_CLASSES = 19
 # src/datasets/dataset.py:60-108 (__ffhq_masks_to_faceParser_mask_detailed); 15, 16, 18 (neck, necklace, cloth) -> background
@@ -189,22 +189,21 @@ def fold_conv_bn(weight, bn):
 def _fold(owner, conv, bn=None, cout_pad=None, smallcin=False):
     """The cached fold of (conv, bn) -- or of conv alone, its outputs zero-padded to cout_pad -- stored on `owner`."""
     tensors = [conv.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-    key = param_key(*tensors) + (cout_pad,)
-    if getattr(owner, "_e4s_fold", None) is None or owner._e4s_fold[0] != key:
-        with torch.no_grad():
-            w = conv.weight.detach().float()
-            if bn is not None:
-                w, b = fold_conv_bn(w, bn)
-                b = b.contiguous()
-            else:
-                b = None
-            if cout_pad is not None and cout_pad > w.shape[0]:
-                w = nn.functional.pad(w, (0, 0, 0, 0, 0, 0, 0, cout_pad - w.shape[0]))
-            f = _Folded(w.contiguous(), b)
-            if smallcin:
-                f.small = K.pack_smallcin(f.weight)
-            owner._e4s_fold = (key, f)
-    return owner._e4s_fold[1]
+
+    def build():
+        w = conv.weight.detach().float()
+        if bn is not None:
+            w, b = fold_conv_bn(w, bn)
+            b = b.contiguous()
+        else:
+            b = None
+        if cout_pad is not None and cout_pad > w.shape[0]:
+            w = nn.functional.pad(w, (0, 0, 0, 0, 0, 0, 0, cout_pad - w.shape[0]))
+        f = _Folded(w.contiguous(), b)
+        if smallcin:
+            f.small = K.pack_smallcin(f.weight)
+        return f
+    return packs.cached(owner, "fold", tensors, build, (cout_pad,))
 
 
 def _cbr(m, **kw):

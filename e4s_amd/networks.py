@@ -12,7 +12,7 @@ from torch import nn
 
 from . import kernels as K
 from .encoders import FSEncoder_PSP
-from .packs import param_key
+from . import packs
 from .stylegan2 import EqualLinear, Generator
 
 
@@ -62,20 +62,18 @@ class Net3(nn.Module):
                 p.requires_grad = False
             for p in self.G.to_rgbs[-(17 - K_) // 2 - 1:].parameters():
                 p.requires_grad = False
-        self._mlp_pack = None
 
     # ---- stacked LocalMLP weights ([R,O,K]) so the 24 small GEMMs become 2 launches -------------
     def _mlp_weights(self):
         ps = [t for m in self.MLPs for t in (m.mlp[0].weight, m.mlp[0].bias, m.mlp[2].weight, m.mlp[2].bias)]
-        key = param_key(*ps)
-        if self._mlp_pack is None or self._mlp_pack[0] != key:
-            with torch.no_grad():
-                w0 = torch.stack([m.mlp[0].weight.detach() for m in self.MLPs]).contiguous()
-                b0 = torch.stack([m.mlp[0].bias.detach() for m in self.MLPs]).contiguous()
-                w2 = torch.stack([m.mlp[2].weight.detach() for m in self.MLPs]).contiguous()
-                b2 = torch.stack([m.mlp[2].bias.detach() for m in self.MLPs]).contiguous()
-            self._mlp_pack = (key, w0, b0, w2, b2)
-        return self._mlp_pack[1:]
+
+        def build():
+            w0 = torch.stack([m.mlp[0].weight.detach() for m in self.MLPs]).contiguous()
+            b0 = torch.stack([m.mlp[0].bias.detach() for m in self.MLPs]).contiguous()
+            w2 = torch.stack([m.mlp[2].weight.detach() for m in self.MLPs]).contiguous()
+            b2 = torch.stack([m.mlp[2].bias.detach() for m in self.MLPs]).contiguous()
+            return w0, b0, w2, b2
+        return packs.cached(self, "mlps", ps, build)
 
     def _encoder_needs_grad(self, img):
         """True when get_style_vectors must build an autograd graph: grad mode on and some encoder parameter trainable

@@ -1,29 +1,27 @@
-"""Cache keys of the re-packed weight images (tap-packed, polyphase, split-bf16, stacked LocalMLPs).
+"""The re-packed weight images of the modules (tap-packed, polyphase, split-bf16, folded BatchNorm, stacked LocalMLPs) and their keys.
 
-A pack is valid for one (storage, version) of its source parameters.  `Tensor._version` advances on every in-place
-update made THROUGH the tensor (optimizer steps, `load_state_dict`, `p.copy_()` under no_grad) but NOT on updates made
-through `p.data` (the reference's EMA, src/utils/torch_utils.py:189-194, writes `p.data.mul_().add_()`).  Code that
-mutates weights behind autograd's back must call `invalidate_packs()` afterwards (the overlay's
-`src.utils.torch_utils.accumulate` does); it bumps a process-wide generation that is part of every key.  A captured
-HIP graph (networks.GraphedFaceSwap) bakes the pack pointers in: re-capture it after any weight change.
+THE RULE: a weight pack is stored on a module through this file or not at all.  All packs of a module live in ONE dict,
+`vars(module)["_e4s_packs"]`: slot -> (key, value, {name: derived image}).  `cached()` fills a slot, `derived()` hangs a lazily built
+image (split-bf16 operand, backward layout, Winograd transform, ...) on the slot's current value, and `invalidate_module_packs()`
+drops the dict.  Nothing else has to know which slots exist, so a new network or a new derived image cannot be forgotten by it.
 
-A captured TRAIN step (train.graphed_g_step / graphed_d_step) reads the packs of a network that another step trains between
-its replays.  A cache hit at capture time would bake in a pack allocated eagerly, which serves the weights of the capture
-forever and is freed by the next eager consumer that re-packs.  So the step's body calls `invalidate_module_packs()` on the
-modules that own a trained parameter: the capture then records the re-pack kernels, into the graph's own memory pool (or
-into the module's lifetime buffers, `_e4s_bufs`, which stay), and every replay re-packs from the weights of the moment."""
+A pack is valid for one (generation, storage, version) of its source tensors (`param_key`).  `Tensor._version` advances on every
+in-place update made THROUGH the tensor (optimizer steps, `load_state_dict`, `p.copy_()` under no_grad) but NOT on updates made
+through `p.data` (the reference's EMA, src/utils/torch_utils.py:189-194, writes `p.data.mul_().add_()`).  Code that mutates weights
+behind autograd's back must call `invalidate_packs()` afterwards (the overlay's `src.utils.torch_utils.accumulate` does); it bumps a
+process-wide generation that is part of every key.  A captured HIP graph (networks.GraphedFaceSwap) bakes the pack pointers in:
+re-capture it after any weight change.  `copy.deepcopy(module)` copies the dict with the original's pointers in its keys, so the
+twin re-packs on first use.
+
+A captured TRAIN step (train.graphed_g_step / graphed_d_step) reads the packs of a network that another step trains between its
+replays.  A cache hit at capture time would bake in a pack allocated eagerly, which serves the weights of the capture forever and
+is freed by the next eager consumer that re-packs.  So the step's body calls `invalidate_module_packs()` on the modules that own a
+trained parameter: the capture then records the re-pack kernels, into the graph's own memory pool (or into the module's lifetime
+buffers, `_e4s_bufs`, which stay), and every replay re-packs from the weights of the moment.  Whatever a captured step re-packs and
+something else holds the address of (the style prologue's job tables) belongs in such a lifetime buffer, written with `out=`."""
+import torch
 
 _GENERATION = 0
-
-# Every attribute that caches a weight pack on a module (keyed on param_key).  A new cache must be listed here, or a captured
-# train step keeps serving it stale (tests/test_host_logic.py checks the package against this list).
-PACK_ATTRS = (
-    "_e4s_pack", "_e4s_wino", "_e4s_split", "_e4s_frag", "_e4s_wt", "_e4s_wt_fwd",         # encoders / encoder_autograd / stylegan2 ConvLayer
-    "_e4s_t", "_e4s_stats", "_e4s_head", "_e4s_small", "_e4s_fold",            # criteria (loss networks)
-    "_e4s_dpacks",                                                             # disc_autograd
-    "_mlp_pack",                                                               # networks.Net3 (stacked LocalMLPs)
-    "_pack",                                                                   # stylegan2.ModulatedConv2d (its data lives in _e4s_bufs)
-)
 
 
 def invalidate_packs():
@@ -34,13 +32,10 @@ def invalidate_packs():
 
 def invalidate_module_packs(modules):
     """Drop the cached weight packs held by each of `modules` (not recursive: pass every module whose packs must go).  The next
-    use re-packs from the current weights.  Lifetime buffers (`_e4s_bufs`) stay: a re-pack writes them in place.  Other modules
-    keep their packs."""
+    use re-packs from the current weights.  Lifetime buffers (`_e4s_bufs`) and the style plan stay: a re-pack writes them in place.
+    Other modules keep their packs."""
     for m in modules:
-        d = vars(m)
-        for name in PACK_ATTRS:
-            if d.get(name) is not None:
-                d[name] = None
+        vars(m).pop("_e4s_packs", None)
 
 
 def modules_owning(root, params):
@@ -52,3 +47,38 @@ def modules_owning(root, params):
 
 def param_key(*tensors):
     return (_GENERATION,) + tuple((t.data_ptr(), t._version) for t in tensors)
+
+
+def cached(owner, slot, tensors, build, extra=()):
+    """The value build() made for this (generation, storage, version) of `tensors` (+ extra: whatever else the value depends on);
+    rebuilt, and every image derived from it dropped, when the key changes.  build runs under torch.no_grad()."""
+    key = (_GENERATION, *[(t.data_ptr(), t._version) for t in tensors], *extra)          # == param_key(*tensors) + extra
+    try:
+        hit = owner.__dict__["_e4s_packs"][slot]
+        if hit[0] == key:
+            return hit[1]
+    except KeyError:
+        pass
+    with torch.no_grad():
+        value = build()
+    owner.__dict__.setdefault("_e4s_packs", {})[slot] = (key, value, {})
+    return value
+
+
+def derived(owner, slot, name, build, key=None):
+    """A lazily built image of the CURRENT value of `slot` (split-bf16 operand, backward layout, Winograd transform, ...): build(value)
+    runs on first use and the image lives and dies with that value.  The slot must be current: call cached() first (a weight pack is
+    read through cached() on every use anyway).  A caller that comes back later than that (an autograd backward) passes the `key` it
+    made the slot current with (param_key(*tensors) + extra) and is refused when the slot has been re-keyed or dropped since, instead of being served another weight's image."""
+    try:
+        have, value, images = owner.__dict__["_e4s_packs"][slot]
+    except KeyError:
+        raise RuntimeError(f"packs.derived: {type(owner).__name__} has no current pack in slot {slot!r} (dropped since packs.cached "
+                           "made it; call cached() first)") from None
+    if key is not None and key != have:
+        raise RuntimeError(f"packs.derived: slot {slot!r} of {type(owner).__name__} was re-packed for other weights since this handle "
+                           "was made (a weight update or invalidate_packs() between a forward and its backward)")
+    image = images.get(name)
+    if image is None:
+        image = images[name] = build(value)
+    return image

@@ -30,7 +30,7 @@ from torch import nn
 
 from . import kernels as K
 from .face_parser import fold_conv_bn
-from .packs import param_key
+from . import packs
 
 MASK_COLORMAP = [0, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 0, 255, 255, 255, 0]    # face_parsing.py:30
 
@@ -92,12 +92,11 @@ class ConvLayer(nn.Module):
     def packed(self):
         """(weights packed for e4s_pconv_f32 in the current precision, bias or None), cached on the layer."""
         f32 = K.sr_f32()
-        key = param_key(*self._tensors()) + (f32,)
-        if getattr(self, "_e4s_pack", None) is None or self._e4s_pack[0] != key:
-            with torch.no_grad():
-                w, b = self.folded()
-                self._e4s_pack = (key, K.pconv_pack(w.contiguous(), f32), b.contiguous() if b is not None else None)
-        return self._e4s_pack[1], self._e4s_pack[2]
+
+        def build():
+            w, b = self.folded()
+            return K.pconv_pack(w.contiguous(), f32), b.contiguous() if b is not None else None
+        return packs.cached(self, "pconv", self._tensors(), build, (f32,))
 
     def run(self, x, y, r0=None, r1=None):
         """The layer on NHWC buffers: x [B,H,W,Cin] -> y [B,Ho,Wo,Cout] (+ r0, + r1 after the activation)."""
@@ -175,13 +174,12 @@ class ParseNet(nn.Module):
     def _small(self):
         """Head [27][Cout] ((ky, kx, ci)-major) and tail [9][Cin][20] (class-minor, zero-padded) weights: layout only, cached."""
         head, tail = self.encoder[0].conv2d, self.out_mask_conv.conv2d
-        key = param_key(head.weight, tail.weight)
-        if getattr(self, "_e4s_small", None) is None or self._e4s_small[0] != key:
-            with torch.no_grad():
-                hw = head.weight.detach().float().permute(2, 3, 1, 0).reshape(27, head.out_channels).contiguous()
-                tw = tail.weight.detach().float().permute(2, 3, 1, 0).reshape(9, tail.in_channels, 19)
-                self._e4s_small = (key, hw, nn.functional.pad(tw, (0, 1)).contiguous())
-        return self._e4s_small[1], self._e4s_small[2]
+
+        def build():
+            hw = head.weight.detach().float().permute(2, 3, 1, 0).reshape(27, head.out_channels).contiguous()
+            tw = tail.weight.detach().float().permute(2, 3, 1, 0).reshape(9, tail.in_channels, 19)
+            return hw, nn.functional.pad(tw, (0, 1)).contiguous()
+        return packs.cached(self, "small", (head.weight, tail.weight), build)
 
     def features_nhwc(self, src, flip=False, taps=None):
         """Everything before out_mask_conv: src uint8 NHWC [B,H,W,3] or fp32 NCHW [B,3,H,W] -> NHWC [B,H',W',C].  taps: a dict that

@@ -41,7 +41,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import kernels as K
-from .packs import param_key
+from . import packs
 
 
 # ---- host arithmetic ----------------------------------------------------------------------------------------------------------------
@@ -196,7 +196,6 @@ class _Native(nn.Module):
 
     def _init_native(self):
         self._e4s_bufs = {}
-        self._e4s_pack = None                                                    # name -> (key, ...): every folded / packed weight
         self._weights_loaded = False
         super().train(False)
 
@@ -221,11 +220,6 @@ class _Native(nn.Module):
         """Drop every cached buffer set (a captured graph that used one keeps it alive)."""
         self._e4s_bufs = {}
 
-    def _cache(self):
-        if self._e4s_pack is None:                                               # also after packs.invalidate_module_packs
-            self._e4s_pack = {}
-        return self._e4s_pack
-
     def _workspace(self, bsz, h, w, device):
         ws = self._e4s_bufs.setdefault((bsz, h, w, str(device)), {})
 
@@ -241,19 +235,16 @@ class _Native(nn.Module):
         output channels are re-ordered (new channel i is old channel perm[i]) before packing."""
         f32 = K.sr_f32()
         tensors = [conv.weight, conv.bias] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-        key = param_key(*tensors) + (f32,)
-        hit = self._cache().get(name)
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                if bn is not None:
-                    w, b = fold_conv_bn_bias(conv.weight.detach().float(), conv.bias.detach().float(), bn)
-                else:
-                    w, b = conv.weight.detach().float(), conv.bias.detach().float()
-                if perm is not None:
-                    w, b = w[perm.to(w.device)], b[perm.to(b.device)]
-                hit = (key, pack(w.contiguous(), f32), b.contiguous())
-            self._cache()[name] = hit
-        return hit[1], hit[2]
+
+        def build():
+            if bn is not None:
+                w, b = fold_conv_bn_bias(conv.weight.detach().float(), conv.bias.detach().float(), bn)
+            else:
+                w, b = conv.weight.detach().float(), conv.bias.detach().float()
+            if perm is not None:
+                w, b = w[perm.to(w.device)], b[perm.to(b.device)]
+            return pack(w.contiguous(), f32), b.contiguous()
+        return packs.cached(self, name, tensors, build, (f32,))
 
     def _rconv(self, name, conv, bn, x, y, perm=None, **kw):
         w, b = self._folded(name, conv, bn, K.rconv_pack, perm)
@@ -329,12 +320,11 @@ class KPDetector(_Native):
         self._init_native()
 
     def _taps(self, device):
-        hit = self._cache().get("aa")
-        if hit is None or hit[0] != str(device):
+        def build():
             taps, step = antialias_taps(self.scale_factor) if self.scale_factor != 1 else (np.ones(1), 1)
-            hit = (str(device), torch.from_numpy(taps).float().to(device), step)
-            self._cache()["aa"] = hit
-        return hit[1], hit[2]
+            return torch.from_numpy(taps).float().to(device), step
+        return packs.cached(self, "aa", (), build, (str(device),))       # no weight pack, a per-device constant: no tensors in its key (an
+                                                                         # invalidate_packs() rebuilds it with the rest, which costs one tiny copy)
 
     def logits_ndhwc(self, frames, taps=None):
         """Device frames [B,H,W,3] (fp32 in [0,1] or uint8) -> (kp logits [B,D,H,W,K], jacobian maps [B,D,H,W,9 J] | None), in the
@@ -444,14 +434,9 @@ class HEEstimator(_Native):
     def _heads(self):
         """w [3 bins + 3 + 3 K, 2048], bias: rows in the reference's OUTPUT order yaw (fc_roll), pitch, roll (fc_yaw), t, exp."""
         fcs = [self.fc_roll, self.fc_pitch, self.fc_yaw, self.fc_t, self.fc_exp]
-        key = param_key(*[t for fc in fcs for t in (fc.weight, fc.bias)])
-        hit = self._cache().get("heads")
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                hit = (key, torch.cat([fc.weight.detach().float() for fc in fcs]).contiguous(),
-                       torch.cat([fc.bias.detach().float() for fc in fcs]).contiguous())
-            self._cache()["heads"] = hit
-        return hit[1], hit[2]
+        return packs.cached(self, "heads", [t for fc in fcs for t in (fc.weight, fc.bias)],
+                            lambda: (torch.cat([fc.weight.detach().float() for fc in fcs]).contiguous(),
+                                     torch.cat([fc.bias.detach().float() for fc in fcs]).contiguous()))
 
     def _bottleneck(self, name, blk, x, new, tag, k):
         """One ResBottleneck on NHWC x into the stage's output buffer k & 1 (x is the other one, or the stage's first conv)."""
@@ -474,9 +459,7 @@ class HEEstimator(_Native):
             return t
         sizes = he_map_sizes(h, w)
         if frames.dtype == torch.uint8:
-            one = self._cache().get("one")
-            if one is None or one.device != frames.device:
-                one = self._cache()["one"] = torch.ones(1, device=frames.device)
+            one = packs.cached(self, "one", (), lambda: torch.ones(1, device=frames.device), (str(frames.device),))      # (a constant, as "aa")
             frames = K.aa_down(frames, one, 1, out=new("x0", h, w, 3))
         x = tap("conv1", self._smallcin("conv1", self.conv1, self.norm1, frames, new("conv1", *sizes[0], self.conv1.out_channels)))
         x = tap("pool", K.retina_pool(x, new("pool", *sizes[1], x.shape[3])))

@@ -40,7 +40,7 @@ import torch
 from torch import nn
 
 from . import kernels as K
-from .packs import param_key
+from . import packs
 from .reenact import DownBlock2d, PoseFrontEnd, UpBlock3d, _Native, _device_frames, _frames, reshape_permutation
 
 
@@ -167,13 +167,7 @@ class _NativeWarp(_Native):
 
     def _cached(self, name, tensors, make):
         """make() cached per version of `tensors` and precision."""
-        key = param_key(*tensors) + (K.sr_f32(),)
-        hit = self._cache().get(name)
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                hit = (key, make())
-            self._cache()[name] = hit
-        return hit[1]
+        return packs.cached(self, name, tensors, make, (K.sr_f32(),))
 
     def _conv3dx(self, name, conv, bn, x, y, cin_pad=None, **kw):
         w, b = self._folded(name, conv, bn, lambda w, f32: K.conv3dx_pack(w, f32, cin_pad))

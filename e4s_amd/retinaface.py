@@ -33,7 +33,7 @@ from torch import nn
 
 from . import kernels as K
 from .face_parser import fold_conv_bn
-from .packs import param_key
+from . import packs
 
 cfg_re50 = {                                                                     # data/config.py:23-41 (the fields inference reads)
     "name": "Resnet50", "min_sizes": [[16, 32], [64, 128], [256, 512]], "steps": [8, 16, 32], "variance": [0.1, 0.2], "clip": False,
@@ -193,54 +193,38 @@ class RetinaFace(nn.Module):
         self.BboxHead = nn.ModuleList(BboxHead(cfg["out_channel"], 2) for _ in range(3))
         self.LandmarkHead = nn.ModuleList(LandmarkHead(cfg["out_channel"], 2) for _ in range(3))
         self._e4s_bufs = {}
-        self._e4s_pack = None                                                    # name -> (key, ...): every folded / packed weight
 
     def release_workspace(self):
         """Drop every cached buffer set (a captured graph that used one keeps it alive)."""
         self._e4s_bufs = {}
 
     # -- weights --------------------------------------------------------------------------------------------------------------
-    def _cache(self):
-        if self._e4s_pack is None:                                               # also after packs.invalidate_module_packs
-            self._e4s_pack = {}
-        return self._e4s_pack
-
     def _unit(self, name, conv, bn):
         """(packed weights, bias) of conv + eval BatchNorm as one conv for e4s_rconv_f32, cached per weight version and precision."""
         f32 = K.sr_f32()
-        key = param_key(conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var) + (f32,)
-        hit = self._cache().get(name)
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                w, b = fold_conv_bn(conv.weight.detach().float(), bn)
-                hit = (key, K.rconv_pack(w.contiguous(), f32), b.contiguous())
-            self._cache()[name] = hit
-        return hit[1], hit[2]
+
+        def build():
+            w, b = fold_conv_bn(conv.weight.detach().float(), bn)
+            return K.rconv_pack(w.contiguous(), f32), b.contiguous()
+        return packs.cached(self, name, (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), build, (f32,))
 
     def _stem(self):
         conv, bn = self.body.conv1, self.body.bn1
-        key = param_key(conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
-        hit = self._cache().get("stem")
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                w, b = fold_conv_bn(conv.weight.detach().float(), bn)
-                hit = (key, K.pack_smallcin(w), b.contiguous())
-            self._cache()["stem"] = hit
-        return hit[1], hit[2]
+
+        def build():
+            w, b = fold_conv_bn(conv.weight.detach().float(), bn)
+            return K.pack_smallcin(w), b.contiguous()
+        return packs.cached(self, "stem", (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), build)
 
     def _heads(self, level):
         """wp [256,32], bias [32]: column anchor * 16 + t, t 0..3 loc, 4..5 conf, 6..15 landmarks (layout only)."""
         convs = [self.BboxHead[level].conv1x1, self.ClassHead[level].conv1x1, self.LandmarkHead[level].conv1x1]
-        key = param_key(*[t for c in convs for t in (c.weight, c.bias)])
-        hit = self._cache().get(f"head{level}")
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                ws = [c.weight.detach().float().reshape(2, -1, 256) for c in convs]           # [anchor][per-anchor][256]
-                bs = [c.bias.detach().float().reshape(2, -1) for c in convs]
-                wp = torch.cat(ws, 1).reshape(32, 256).t().contiguous()
-                hit = (key, wp, torch.cat(bs, 1).reshape(32).contiguous())
-            self._cache()[f"head{level}"] = hit
-        return hit[1], hit[2]
+
+        def build():
+            ws = [c.weight.detach().float().reshape(2, -1, 256) for c in convs]           # [anchor][per-anchor][256]
+            bs = [c.bias.detach().float().reshape(2, -1) for c in convs]
+            return torch.cat(ws, 1).reshape(32, 256).t().contiguous(), torch.cat(bs, 1).reshape(32).contiguous()
+        return packs.cached(self, f"head{level}", [t for c in convs for t in (c.weight, c.bias)], build)
 
     # -- execution ------------------------------------------------------------------------------------------------------------
     def _workspace(self, bsz, h, w, device):

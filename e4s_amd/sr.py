@@ -20,7 +20,7 @@ with strict=True.  The modules hold parameters only; execution is on NHWC buffer
     conv_last, clamp, * 255, round, uint8, RGB -> BGR  e4s_rrdb_tail_f32 (one pass)
 
 Arithmetic follows kernels.PRECISION: "f32" runs the exact fp32 MFMA, "bf16x3" and "auto" the split-bf16 path (three bf16 MFMAs per
-product, fp32 accumulate).  Weights are re-packed once per weight version and precision (cached on each conv as `_e4s_pack`).  The
+product, fp32 accumulate).  Weights are re-packed once per weight version and precision (cached on each conv: packs.cached).  The
 working set -- three 160-channel buffers at the input resolution, one 32-channel copy of conv_first's output, two 32-channel buffers
 at 4x -- belongs to the RRDBNet, one set per input shape; nothing else is allocated after the first call at a shape but the result.
 There is no CPU path; scales 2 and 1 (the reference's pixel-unshuffle variants) are not provided."""
@@ -31,7 +31,7 @@ import torch
 from torch import nn
 
 from . import kernels as K
-from .packs import param_key
+from . import packs
 
 
 class ResidualDenseBlock(nn.Module):
@@ -59,25 +59,20 @@ class RRDB(nn.Module):
 def _packed(conv):
     """(weights packed for e4s_rrdb_conv_f32 in the current precision, bias), cached on the conv."""
     f32 = K.sr_f32()
-    key = param_key(conv.weight) + (f32,)
-    if getattr(conv, "_e4s_pack", None) is None or conv._e4s_pack[0] != key:
-        with torch.no_grad():
-            conv._e4s_pack = (key, K.rrdb_pack(conv.weight.detach().float().contiguous(), f32))
-    return conv._e4s_pack[1], conv.bias.detach()
+    w = packs.cached(conv, "rrdb", (conv.weight,), lambda: K.rrdb_pack(conv.weight.detach().float().contiguous(), f32), (f32,))
+    return w, conv.bias.detach()
 
 
 def _packed_small(conv):
     """conv_first [32,3,3,3] -> [27][32] ((ky, kx, ci)-major); conv_last [3,32,3,3] -> [9][3][32]: layout only, cached on the conv."""
-    key = param_key(conv.weight)
-    if getattr(conv, "_e4s_small", None) is None or conv._e4s_small[0] != key:
-        with torch.no_grad():
-            w = conv.weight.detach().float()
-            if w.shape[1] == 3:
-                p = w.permute(2, 3, 1, 0).reshape(27, w.shape[0])
-            else:
-                p = w.permute(2, 3, 0, 1).reshape(9, w.shape[0], w.shape[1])
-            conv._e4s_small = (key, p.contiguous())
-    return conv._e4s_small[1], conv.bias.detach()
+    def build():
+        w = conv.weight.detach().float()
+        if w.shape[1] == 3:
+            p = w.permute(2, 3, 1, 0).reshape(27, w.shape[0])
+        else:
+            p = w.permute(2, 3, 0, 1).reshape(9, w.shape[0], w.shape[1])
+        return p.contiguous()
+    return packs.cached(conv, "small", (conv.weight,), build), conv.bias.detach()
 
 
 def dense_block(rdb, buf, out, *, outer=None):

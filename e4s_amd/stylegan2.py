@@ -167,7 +167,7 @@ def polyphase_upconv_weights(w, blur_kernel):
     return torch.stack(phases, 0).contiguous()
 
 
-from .packs import param_key as _param_key  # noqa: E402
+from . import packs  # noqa: E402
 
 
 class ModulatedConv2d(nn.Module):
@@ -193,7 +193,6 @@ class ModulatedConv2d(nn.Module):
         self.modulation = EqualLinear(style_dim, in_channel, bias_init=1)
         self.demodulate = demodulate
         self.fused = fused
-        self._pack = None
 
     def _buf(self, name, shape, device):
         """ONE buffer per weight pack for the module's lifetime: re-packs after a weight update write in place.  Nothing is allocated
@@ -209,47 +208,42 @@ class ModulatedConv2d(nn.Module):
 
     def packed(self):
         """Returns dict(w=[ncls,taps,Cout,Cin], wsq=[Cout,Cin] | None, w_rgb=[Cout,Cin] for 1x1)."""
-        key = _param_key(self.weight) + ((_param_key(self.blur.kernel)) if self.upsample else ())
-        if self._pack is not None and self._pack["key"] == key:
-            return self._pack
-        with torch.no_grad():
-            w = self.weight.detach()[0].float()                                  # [Cout,Cin,k,k]
-            cout, cin, k, _ = w.shape
-            dev = w.device
-            pack = {"key": key}
-            if k == 1:
-                pack["w"] = w.reshape(1, 1, cout, cin).contiguous()
-            elif not self.upsample:
-                pack["w"] = K.pack_taps(w.contiguous(), out=self._buf("w", (1, 9, cout, cin), dev))
-            else:
-                # same math as polyphase_upconv_weights() below (the CPU-tested statement of it)
-                pack["w"] = K.polyphase_weights(w.contiguous(), self.blur.kernel.detach().float(), out=self._buf("w", (4, 9, cout, cin), dev))
-                pack["w3"] = K.pack_taps(w.contiguous(), out=self._buf("w3", (1, 9, cout, cin), dev))   # plain taps: exact tile-fused up-conv
-            pack["wsq"] = K.weight_sqsum(w.contiguous(), out=self._buf("wsq", (cout, cin), dev)) if self.demodulate else None
-        self._pack = pack
+        return packs.cached(self, "w", (self.weight, self.blur.kernel) if self.upsample else (self.weight,), self._build_pack)
+
+    def _build_pack(self):
+        w = self.weight.detach()[0].float()                                  # [Cout,Cin,k,k]
+        cout, cin, k, _ = w.shape
+        dev = w.device
+        pack = {}
+        if k == 1:
+            pack["w"] = w.reshape(1, 1, cout, cin).contiguous()
+        elif not self.upsample:
+            pack["w"] = K.pack_taps(w.contiguous(), out=self._buf("w", (1, 9, cout, cin), dev))
+        else:
+            # same math as polyphase_upconv_weights() below (the CPU-tested statement of it)
+            pack["w"] = K.polyphase_weights(w.contiguous(), self.blur.kernel.detach().float(), out=self._buf("w", (4, 9, cout, cin), dev))
+            pack["w3"] = K.pack_taps(w.contiguous(), out=self._buf("w3", (1, 9, cout, cin), dev))   # plain taps: exact tile-fused up-conv
+        pack["wsq"] = K.weight_sqsum(w.contiguous(), out=self._buf("wsq", (cout, cin), dev)) if self.demodulate else None
         return pack
 
-    def _derived(self, name, build):
-        """A lazily built image of the current pack (split-bf16 operands, backward layouts), in its lifetime buffer."""
-        pk = self.packed()
-        if name not in pk:
-            with torch.no_grad():
-                pk[name] = build(pk)
-        return pk[name]
+    def image(self, name, build):
+        """build(packed()) in its lifetime buffer: a lazily built image of the current pack (split-bf16 operands, backward layouts)."""
+        self.packed()
+        return packs.derived(self, "w", name, build)
 
     def subpixel_split_weights(self):
         """Split-bf16 image of the sub-pixel GEMM operand of e4s_upconv_bf16x3_f32 (exact up-conv; cached with the pack)."""
         cout, cin = self.out_channel, self.in_channel
-        return self._derived("w_sub_split", lambda pk: K.subpixel_weights(
+        return self.image("w_sub_split", lambda pk: K.subpixel_weights(
             self.weight.detach()[0].float().contiguous(), out=self._buf("w_sub_split", (cin // 32, cout // 32, 9, 32, 32), self.weight.device)))
 
     def split_weights(self):
         """Split-bf16 image of packed()["w"] for e4s_conv_bf16x3_f32 (built on first use, cached with the pack)."""
-        return self._derived("w_split", lambda pk: K.split_bf16x2(pk["w"], out=self._buf("w_split", tuple(pk["w"].shape), pk["w"].device)))
+        return self.image("w_split", lambda pk: K.split_bf16x2(pk["w"], out=self._buf("w_split", tuple(pk["w"].shape), pk["w"].device)))
 
     def split_weights16(self):
         """16-channel-chunk split image of packed()["w"] for e4s_conv_region_bf16x3_f32 (masked layers; cached with the pack)."""
-        return self._derived("w_split16", lambda pk: K.split16_bf16x2(pk["w"], out=self._buf("w_split16", K.split16_shape(pk["w"].shape), pk["w"].device)))
+        return self.image("w_split16", lambda pk: K.split16_bf16x2(pk["w"], out=self._buf("w_split16", K.split16_shape(pk["w"].shape), pk["w"].device)))
 
     def scatter_taps(self):
         """packed()["w"] [ncls,9,Cout,Cin] as the operand of the scatter-form input gradient (autograd.styled_conv_backward, masked
@@ -260,14 +254,14 @@ class ModulatedConv2d(nn.Module):
             wg = self._buf("wg", (ncls, 1, 9 * cin, cout), pk["w"].device)
             wg.view(ncls, 9, cin, cout).copy_(pk["w"].permute(0, 1, 3, 2))
             return wg, K.split_bf16x2(wg, out=self._buf("wg_split", (ncls, 1, 9 * cin, cout), pk["w"].device))
-        return self._derived("wg", build)
+        return self.image("wg", build)
 
     def bwd_taps(self):
         """packed()["w"] in the backward layout [ncls,9,Cin,Cout], taps flipped (e4s_conv_bwd_mfma_f32's operand)."""
         def build(pk):
             ncls, _, cout, cin = pk["w"].shape
             return K.pack_taps_bwd(pk["w"], out=self._buf("wt", (ncls, 9, cin, cout), pk["w"].device))
-        return self._derived("wt", build)
+        return self.image("wt", build)
 
     def forward(self, input, style):
         """Drop-in single-style forward (NCHW in/out), model.py:242-320."""
@@ -754,18 +748,14 @@ class Generator(nn.Module):
 # ---- ConvLayer on the HIP kernels (Discriminator, GPEN encoder) ----------------------------------------------------------
 def _packed_equal_conv(conv, cin_pad):
     """EqualConv2d weight * scale (model.py:117-123) tap-packed [1,k*k,Cout,cin_pad] (input channels zero-padded to the
-    kernels' 32-channel K step), + its split-bf16 image; cached on the module."""
-    key = _param_key(conv.weight) + (cin_pad,)
-    pk = getattr(conv, "_e4s_pack", None)
-    if pk is None or pk["key"] != key:
-        with torch.no_grad():
-            w = conv.weight.detach().float() * conv.scale
-            cout, cin, k, _ = w.shape
-            if cin_pad != cin:
-                w = torch.cat([w, w.new_zeros(cout, cin_pad - cin, k, k)], 1)
-            pk = {"key": key, "w": K.pack_taps(w.contiguous())}
-        conv._e4s_pack = pk
-    return pk
+    kernels' 32-channel K step); cached on the module."""
+    def build():
+        w = conv.weight.detach().float() * conv.scale
+        cout, cin, k, _ = w.shape
+        if cin_pad != cin:
+            w = torch.cat([w, w.new_zeros(cout, cin_pad - cin, k, k)], 1)
+        return K.pack_taps(w.contiguous())
+    return packs.cached(conv, "equal", (conv.weight,), build, (cin_pad,))
 
 
 def conv_layer_nhwc(layer, x, x_is_nchw=False):
@@ -791,22 +781,20 @@ def conv_layer_nhwc(layer, x, x_is_nchw=False):
             raise NotImplementedError("NCHW input is only accepted by the 1x1 stem ConvLayer")
         return K.conv1x1_small(x, conv.weight.detach().reshape(cout, cin), bias, conv.scale, act, alpha, gain)
     cx = x.shape[3]
-    pk = _packed_equal_conv(conv, cx)                   # cx > cin: the caller padded the activation (513 -> 544)
+    wp = _packed_equal_conv(conv, cx)                   # cx > cin: the caller padded the activation (513 -> 544)
     if cx < cin or cx % 32:
         raise RuntimeError(f"ConvLayer on {cx} channels: need a multiple of 32 >= {cin}")
     kw = dict(bias=bias, act=act, alpha=alpha, gain=gain)
     b, h, w, _ = x.shape
 
     def split():
-        if "w_split" not in pk:
-            pk["w_split"] = K.split_bf16x2(pk["w"])
-        return pk["w_split"]
+        return packs.derived(conv, "equal", "split", K.split_bf16x2)
     if conv.stride == 1:
         if k != 3 or conv.padding != 1:
             raise NotImplementedError("stride-1 ConvLayers are 3x3 / padding 1 (model.py:701-703)")
         if K.want_bf16x3(b, h, w, cx, cout):
-            return K.conv_mfma(x, pk["w"], cout, w_split=split(), **kw)
-        return K.conv_mfma(x, pk["w"], cout, **kw)
+            return K.conv_mfma(x, wp, cout, w_split=split(), **kw)
+        return K.conv_mfma(x, wp, cout, **kw)
     if blur is None or conv.stride != 2 or conv.padding != 0 or k not in (1, 3):
         raise NotImplementedError("down-sampling ConvLayers are Blur + stride-2 padding-0 convs (model.py:683-700)")
     xb = K.upfirdn2d_nhwc(x, blur.kernel, pad=blur.pad)
@@ -815,10 +803,9 @@ def conv_layer_nhwc(layer, x, x_is_nchw=False):
     gk = dict(istride=2, ntaps=k * k, anchors=anchors, tap_shift=1 if k == 3 else 0, **kw)
     tiles = (b * anchors[0] * anchors[1] + 255) // 256 * (cout // 128 if cout % 128 == 0 else 0)
     if K.PRECISION != "f32" and cout % 128 == 0 and (K.PRECISION == "bf16x3" or tiles >= K.BF16X3_MIN_BLOCKS):
-        if "w_frag" not in pk:
-            pk["w_frag"] = K.gather_frag_bf16x2(pk["w"])
-        return K.conv_mfma(xb, pk["w"], cout, w_split=split(), w_frag=pk["w_frag"], **gk)
-    return K.conv_mfma(xb, pk["w"], cout, **gk)
+        frag = packs.derived(conv, "equal", "frag", K.gather_frag_bf16x2)
+        return K.conv_mfma(xb, wp, cout, w_split=split(), w_frag=frag, **gk)
+    return K.conv_mfma(xb, wp, cout, **gk)
 
 
 def equal_linear_lrelu(lin, x):

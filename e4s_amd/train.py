@@ -22,6 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from . import kernels as K
+from . import packs
 from . import tape as _tape
 
 
@@ -285,7 +286,6 @@ class TrainIteration:
     def _invalidate_net_packs(self):
         """Drop the weight packs of every module of the net that owns a trained parameter (frozen modules -- a frozen generator --
         keep theirs: a captured step must not re-pack them on every replay)."""
-        from . import packs
         packs.invalidate_module_packs(packs.modules_owning(self.core, self._net_trainable))
 
     def graphed_g_step(self, img, onehot, warmup=2, fork_losses_in_graph=None, **fwd):
@@ -304,7 +304,6 @@ class TrainIteration:
         rest: its packs are re-packed in place inside the graph (ModulatedConv2d's lifetime buffers), the style prologue's job tables
         depend on addresses only (Generator._style_plan) and are built by the warm-up steps."""
         from .optim import GraphedStep
-        from . import disc_autograd
         if self.core is not self.net:
             raise RuntimeError("graphed_g_step: torch's DistributedDataParallel reducer cannot be held by a stream capture; pass the "
                                "bare Net3 and a ddp.GradAverager (its bucket all-reduces are captured with the step), or use g_step()")
@@ -313,7 +312,7 @@ class TrainIteration:
             self.forget_targets()
             self._invalidate_net_packs()
             if self.disc is not None:
-                disc_autograd.invalidate_packs(self.disc)
+                packs.invalidate_module_packs(self.disc.modules())
             # Inside the capture only ONE loss network -- the identity net, the longest chain -- gets a side stream (the eager step forks them all):
             # a replayed hipGraph is spread over several hardware queues and pays for every cross-queue edge.  Batch-2 step at 1024^2, alternations on
             # one box, ms: all four terms forked 60.6-62.6 (bimodal), one chain 53.5-54.4, LPIPS alone on the side 52.3-52.5, **ID alone 51.2-51.3**,
@@ -340,21 +339,19 @@ class TrainIteration:
         the graph's own pool, and every replay re-packs from the weights of the moment.  Without that the capture would hit the cache
         and bake in the packs of the last eager step -- stale after the next G step, and freed by the next eager consumer of the net."""
         from .optim import GraphedStep
-        from . import disc_autograd
 
         def body():
             self._invalidate_net_packs()
-            disc_autograd.invalidate_packs(self.disc)
+            packs.invalidate_module_packs(self.disc.modules())
             return self.d_step(img, onehot, **fwd)
         return GraphedStep(self.opt_d, body, warmup=warmup)
 
     def graphed_r1_step(self, img, warmup=1):
         """The R1 step (coach.py:309-319: the second-order pass) as ONE HIP graph; same requirements as graphed_d_step."""
         from .optim import GraphedStep
-        from . import disc_autograd
 
         def body():
-            disc_autograd.invalidate_packs(self.disc)
+            packs.invalidate_module_packs(self.disc.modules())
             return self.r1_step(img)
         return GraphedStep(self.opt_d, body, warmup=warmup)
 

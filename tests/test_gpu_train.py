@@ -612,10 +612,9 @@ def test_graphed_g_step_equals_the_eager_loop(train_G):
 
 
 def _pack_tensors(net, keep=False):
-    """{data_ptr: (shape, dtype)} of every tensor held in a weight-pack cache of `net` (packs.PACK_ATTRS; lifetime buffers excluded):
-    no tensor is returned, so the caller keeps no pack alive.  keep=True: the list of the tensors themselves."""
-    from e4s_amd import packs
-
+    """{data_ptr: (shape, dtype)} of every tensor held in a weight-pack cache of `net` (the one dict e4s_amd.packs keeps on each module;
+    the `_e4s_bufs` registry of lifetime buffers is not walked): no tensor is returned, so the caller keeps no pack alive.  keep=True:
+    the list of the tensors themselves."""
     def walk(v):
         if torch.is_tensor(v):
             yield v
@@ -625,9 +624,7 @@ def _pack_tensors(net, keep=False):
         elif isinstance(v, dict):
             for x in v.values():
                 yield from walk(x)
-        elif hasattr(v, "packs") and hasattr(v, "key"):          # disc_autograd._PackCache
-            yield from walk(v.packs)
-    held = [t for m in net.modules() for name in packs.PACK_ATTRS for t in walk(vars(m).get(name))]
+    held = [t for m in net.modules() for t in walk(vars(m).get("_e4s_packs"))]
     return held if keep else {t.data_ptr(): (tuple(t.shape), t.dtype) for t in held}
 
 

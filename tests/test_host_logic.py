@@ -1,5 +1,6 @@
 """CPU tests of host-side logic that never touches the GPU: weight re-packing, state_dict
 compatibility, the C-ABI surface of libe4s_hip.so, sharding arithmetic."""
+import copy
 import ctypes
 import os
 import re
@@ -500,9 +501,11 @@ def test_captured_train_steps_repack_every_module_another_step_trains(monkeypatc
     from e4s_amd import optim, packs
     from e4s_amd.train import TrainIteration
 
-    def dress(m):                                          # every kind of cached pack, as the real modules hold them
-        for name in packs.PACK_ATTRS:
-            setattr(m, name, ("key", "old"))
+    def dress(m):                                          # cached packs as the real modules hold them: several slots, one with a derived image
+        vars(m).pop("_e4s_packs", None)
+        for slot in ("taps", "fold", "w"):
+            packs.cached(m, slot, (), lambda: "old " + slot, ("key",))
+        packs.derived(m, "taps", "split", lambda v: v + ", split")
         m.__dict__["_e4s_bufs"] = {"w": "lifetime"}
         m._e4s_style_plan = {"key": "addresses"}
         return m
@@ -523,7 +526,7 @@ def test_captured_train_steps_repack_every_module_another_step_trains(monkeypatc
             self.seen = []
 
         def forward(self, img, onehot, **kw):
-            self.seen.append({n: getattr(m, "_e4s_pack") for n, m in self.named_modules()})
+            self.seen.append({n: copy.deepcopy(vars(m).get("_e4s_packs")) for n, m in self.named_modules()})      # None: nothing cached
             return img * self.enc[0].weight * self.enc[1].weight * self.mlp.weight * self.G[0].weight, None
 
     class Disc(torch.nn.Module):
@@ -541,6 +544,9 @@ def test_captured_train_steps_repack_every_module_another_step_trains(monkeypatc
             body()
     monkeypatch.setattr(optim, "GraphedStep", Stub)
     net, disc = Net(), Disc()
+    assert [n for n, _ in disc.named_modules()] == ["", "lin"]
+    old = copy.deepcopy(vars(dress(Leaf()))["_e4s_packs"])
+    assert set(old) == {"taps", "fold", "w"} and old["taps"][1:] == ("old taps", {"split": "old taps, split"})
     for p in list(net.G[1].parameters()) + list(net.style.parameters()):
         p.requires_grad = False
     trained = {"", "enc", "enc.0", "enc.1", "mlp", "G", "G.0"}
@@ -550,7 +556,7 @@ def test_captured_train_steps_repack_every_module_another_step_trains(monkeypatc
                         torch.optim.SGD(disc.parameters(), lr=1e-3))
     img = torch.rand(2, 3, 4, 4)
     for step in ("d", "g"):
-        for _, m in net.named_modules():
+        for m in list(net.modules()) + list(disc.modules()):
             dress(m)
         net.seen.clear()
         if step == "d":
@@ -560,26 +566,27 @@ def test_captured_train_steps_repack_every_module_another_step_trains(monkeypatc
         assert calls[-1] is (it.opt_d if step == "d" else it.opt)
         assert len(net.seen) == 1
         for n, m in net.named_modules():
-            assert net.seen[0][n] == (None if n in trained else ("key", "old")), (step, n)        # dropped before the forward read it
-            for name in packs.PACK_ATTRS:
-                assert getattr(m, name) == (None if n in trained else ("key", "old")), (step, n, name)
+            assert net.seen[0][n] == (None if n in trained else old), (step, n)        # dropped before the forward read it
+            assert vars(m).get("_e4s_packs") == (None if n in trained else old), (step, n)
             assert m._e4s_bufs == {"w": "lifetime"} and m._e4s_style_plan == {"key": "addresses"}, (step, n)
+        for m in disc.modules():                             # D's packs go in both steps (the D step trains it between G replays)
+            assert "_e4s_packs" not in vars(m) and m._e4s_bufs == {"w": "lifetime"}, step
 
 
-def test_every_module_cache_of_the_package_is_a_listed_pack_or_a_known_non_pack():
-    """packs.invalidate_module_packs drops the attributes listed in packs.PACK_ATTRS; a cache added under another name would escape it
-    and a captured train step would serve it stale.  Every `._e4s_*` / `._*pack*` attribute the package assigns is listed, or is one
-    of the caches that must survive (lifetime buffers, address-keyed job tables, a structural check)."""
-    from e4s_amd import packs
+def test_the_package_stores_no_module_cache_outside_packs_but_the_three_survivors():
+    """packs.invalidate_module_packs drops the one dict that packs.cached / packs.derived keep on a module; a cache stored on a module in
+    any other way would escape it and a captured train step would serve it stale.  So outside packs.py the package assigns no
+    `._e4s_*` / `._*pack*` attribute but the caches that must survive (lifetime buffers, address-keyed job tables, a structural
+    check), and never reaches into that dict."""
     keep = {"_e4s_bufs", "_e4s_style_plan", "_e4s_style_ok"}
     pkg = os.path.join(ROOT, "e4s_amd")
     found = set()
     for dirpath, _, files in os.walk(pkg):
         for f in files:
-            if f.endswith(".py"):
+            if f.endswith(".py") and os.path.join(dirpath, f) != os.path.join(pkg, "packs.py"):
                 src = open(os.path.join(dirpath, f)).read()
                 found |= set(re.findall(r"\.(_e4s_\w+|_\w*pack\w*)\s*=[^=]", src))
                 found |= set(re.findall(r"setdefault\(\"(_e4s_\w+)\"", src))
-    assert "_e4s_pack" in found and "_mlp_pack" in found and "_e4s_bufs" in found
-    assert found - keep <= set(packs.PACK_ATTRS), sorted(found - keep - set(packs.PACK_ATTRS))
-    assert not keep & set(packs.PACK_ATTRS)
+                assert "_e4s_packs" not in src, f
+    assert found == keep, sorted(found ^ keep)
+    assert "_e4s_packs" in open(os.path.join(pkg, "packs.py")).read()
